@@ -13,6 +13,10 @@ axis is sharded (weak scaling: B per GPU fixed), gradients all-reduced over RCCL
 
 Prints ONE JSON line on rank 0 (metric, roofline of the dominant kernel measured
 live with HIP events, CPU baseline = the oracle timed on this host's cores).
+
+--dump-outputs DIR writes what the last timed step computed (losses, log-posteriors,
+the trained parameters and running statistics) as DIR/<name>.npy, so that two
+builds can be compared output for output on the same arguments.
 """
 import argparse
 import importlib
@@ -27,6 +31,8 @@ if ROOT not in sys.path:
 
 import torch  # noqa: E402
 
+PREWARM_STEPS_FOR_DUMP = 64        # --dump-outputs: the pre-warm in steps (~1.1 s of the headline step)
+DUMP_BYTES = 60 << 20               # --dump-outputs: data bytes in all (64 MB with the .npy headers and margin)
 PEAK = {"bf16": 2500.0, "fp32": 157.3}  # dense MFMA TFLOP/s, MI355X_MICROARCH.md
 HBM_PEAK = 8000.0                      # GB/s
 
@@ -83,7 +89,17 @@ def parse():
                     help="report every timed step's GPU time (HIP event per step) and host enqueue time, not only their summary")
     ap.add_argument("--launch-check", action="store_true",
                     help="rendezvous only: every rank joins, one all-reduce, rank 0 prints {\"n_gpus\": world} (tests)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float32 / float64, at "
+                         "most 64 MB in all: larger outputs as a fixed, seeded sample of their elements).  The pre-warm then "
+                         "runs a fixed %d steps instead of a time budget, so that the same arguments give the same state "
+                         "before the timed region" % PREWARM_STEPS_FOR_DUMP)
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup < 0:
+        ap.error("--warmup must not be negative")
+    return args
 
 
 class Trainer:
@@ -126,6 +142,7 @@ class Trainer:
         self.batches = [self.R.synthetic_batch(rcp, self.T, self.B, 4234 + 17 * rank + i, "cuda") for i in range(2)]
         self.n_params = sum(p.numel() for n in self.nns.values() for p in n.parameters())
         self.graphed = None
+        self.keep_outs, self.last_outs = False, None  # --dump-outputs: the forward_model outputs of the last step
         self.fence = self.F.StepFence()  # as core.run_nn_dp: eager steps, at most PK_STEPS_IN_FLIGHT ahead of the GPU
 
     def step(self, i):
@@ -150,6 +167,8 @@ class Trainer:
             for o in self.opts.values():
                 o.zero_grad()
             outs["loss_final"].backward()
+        if self.keep_outs:
+            self.last_outs = outs
         self.reducer.finish()
         for o in self.opts.values():
             o.step()
@@ -510,12 +529,13 @@ def workload_name(recipe, tr):
                tr.rcp["n_cd"], tr.rcp["n_mono"]))
 
 
-def measure(args, rank, world, steps, warmup):
+def measure(args, rank, world, steps, warmup, dump_dir=None):
     """One configuration: build, warm up, time exactly `steps` steps between barriers, profile two more steps.
-    Returns (record, Trainer)."""
+    dump_dir: write the last timed step's outputs there (dump_outputs).  Returns (record, Trainer)."""
     import torch.distributed as dist
 
     tr = Trainer(args, rank, world)
+    dump = bool(dump_dir)
 
     def barrier():
         if world > 1:
@@ -535,7 +555,9 @@ def measure(args, rank, world, steps, warmup):
     if use_graph:
         if warmup == 0:
             tr.step(0)  # lazy one-time initialisation must not land inside the capture
+        tr.keep_outs = dump  # a replay rewrites the captured step's own output tensors
         tr.enable_graph()
+        tr.keep_outs = False
         tr.step(0)      # first replay (graph upload) outside the timed region
     # Untimed, time-based pre-warm, behind the counted warm-up and the graph capture: the driver's command is a FRESH process on a fresh box with
     # --warmup 5, i.e. 0.1 s of GPU work before the clock starts.  The steps are enqueued without host syncs so that
@@ -543,7 +565,14 @@ def measure(args, rank, world, steps, warmup):
     prewarm_s = getattr(args, "prewarm_s", -1.0)
     prewarm_s = 1.5 if prewarm_s < 0 else prewarm_s
     n_pre = 0
-    if prewarm_s > 0:
+    if prewarm_s > 0 and dump:  # a fixed number of steps: the timed region starts from the same state in every run
+        for _ in range(PREWARM_STEPS_FOR_DUMP // 4):
+            for _ in range(4):
+                tr.step(n_pre)
+                n_pre += 1
+            torch.cuda.synchronize()
+        barrier()
+    elif prewarm_s > 0:
         t_pre = time.perf_counter()
         go = True
         while go:
@@ -569,6 +598,8 @@ def measure(args, rank, world, steps, warmup):
         evs, marks = [ev0], [time.perf_counter()]
         t0 = time.perf_counter()
         for i in range(steps):
+            if dump and tr.graphed is None:
+                tr.keep_outs = i == steps - 1
             loss = tr.step(i)
             if losses is not None:
                 losses.append(loss)
@@ -586,6 +617,9 @@ def measure(args, rank, world, steps, warmup):
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             dt = float(t)
         regions.append(dt)
+    tr.keep_outs = False
+    if dump and rank == 0:  # before anything else steps the model (the profiled steps below do)
+        out_dump = dump_outputs(tr, dump_dir)
     dt = sorted(regions)[len(regions) // 2]  # the median region (one region: that one)
     log("%s/%s timed region(s) done: %s s" % (args.recipe, args.prec, ["%.3f" % r for r in regions]))
     _lib = importlib.import_module("pytorch-kaldi_amd._lib")
@@ -604,8 +638,10 @@ def measure(args, rank, world, steps, warmup):
                    "params": tr.n_params},
         "loss_final": round(float(loss), 5),
     }
-    out["config"]["prewarm_s"] = prewarm_s
+    out["config"]["prewarm_s"] = prewarm_s if not dump else None
     out["config"]["prewarm_steps"] = n_pre
+    if dump and rank == 0:
+        out["dump_outputs"] = out_dump
     mid = sorted(range(len(regions)), key=lambda k: regions[k])[len(regions) // 2]
     if len(step_events[mid]) > 1:
         evs, marks = step_events[mid], host_marks[mid]
@@ -655,6 +691,58 @@ def measure(args, rank, world, steps, warmup):
                                            sorted(summ.items(), key=lambda kv: -kv[1]["ms_per_step"])}
         out["whole_step_tflops"] = round(total_flops / (ms_per_step * 1e-3) / 1e12, 3)
     return out, tr
+
+
+def dump_outputs(tr, d):
+    """--dump-outputs: what a caller of the timed step receives after the last timed step, as d/<name>.npy - every value
+    the recipe's model lines define (networks' outputs such as the per-frame log-posteriors, the losses, the frame error
+    rate) and the trained networks (param.<arch>.<name>: weights after the optimizer step; buffer.<arch>.<name>: running
+    statistics).  float64 stays float64, everything else is written as float32.  When the whole exceeds DUMP_BYTES, every
+    array of more than 4096 elements is replaced by a sample of its flattened elements, its share of the budget in
+    proportion to its size: one position in each of k equal strata, drawn by a generator seeded with the array's name -
+    the same ascending positions in every run with the same arguments.  Returns a summary for the JSON line."""
+    import zlib
+
+    import numpy as np
+
+    if torch.cuda.is_available():
+        torch.cuda.synchronize()
+    outs = tr.last_outs or {}
+    arrays = []
+    for line in tr.rcp["model"]:  # "name=op(args)": every value the model's lines define, in their order
+        k = line.split("=")[0].strip()
+        if torch.is_tensor(outs.get(k)) and outs[k].is_floating_point():
+            arrays.append((k, outs[k].detach()))
+    if not arrays:
+        raise RuntimeError("--dump-outputs: the last timed step left no outputs")
+    for arch in sorted(tr.nns):
+        net = tr.nns[arch]
+        arrays += [("param.%s.%s" % (arch, n), p.detach()) for n, p in net.named_parameters()]
+        arrays += [("buffer.%s.%s" % (arch, n), b.detach()) for n, b in net.named_buffers() if b.is_floating_point()]
+    budget = DUMP_BYTES // 4
+    total = sum(t.numel() for _, t in arrays)
+    small = sum(t.numel() for _, t in arrays if t.numel() <= 4096)
+    share = 1.0 if total <= budget else (budget - small) / float(total - small)
+    os.makedirs(d, exist_ok=True)
+    files, sampled, nbytes = 0, [], 0
+    for name, t in arrays:
+        n = t.numel()
+        k = n if n <= 4096 or share >= 1.0 else max(1, int(n * share))
+        dt_ = np.float64 if t.dtype == torch.float64 else np.float32
+        if k < n:
+            lo = np.arange(k, dtype=np.int64) * n // k
+            hi = np.arange(1, k + 1, dtype=np.int64) * n // k
+            idx = lo + (np.random.default_rng(zlib.crc32(name.encode())).random(k) * (hi - lo)).astype(np.int64)
+            a = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+            sampled.append(name)
+        else:
+            a = t
+        a = a.to(torch.float64 if dt_ is np.float64 else torch.float32).cpu().numpy()
+        np.save(os.path.join(d, name + ".npy"), a)
+        files += 1
+        nbytes += a.nbytes
+    return {"dir": d, "files": files, "bytes": nbytes, "sampled": sampled,
+            "note": "the last timed step's outputs; sampled arrays hold a seeded sample of their flattened elements"}
 
 
 def release(tr):
@@ -852,7 +940,7 @@ def main():
         return
     if world != args.gpus and world > 1:
         args.gpus = world
-    out, tr = measure(args, rank, world, args.steps, args.warmup)
+    out, tr = measure(args, rank, world, args.steps, args.warmup, dump_dir=args.dump_outputs)
     headline = args.recipe == "timit_ligru" and args.prec == "bf16" and (args.T, args.B) == (500, 128) and args.layers is None
     if rank == 0:
         out["entry_points_note"] = ("HIP events around every C-ABI call of two extra eager steps on ONE stream; the timed "

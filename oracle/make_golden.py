@@ -973,6 +973,88 @@ def cfg_case(name):
     print("wrote %s (%d bytes)" % (path, os.path.getsize(path)))
 
 
+DROPIN_RECIPES = [("cfg/TIMIT_baselines/TIMIT_liGRU_fmllr.cfg", 40), ("cfg/TIMIT_baselines/TIMIT_LSTM_fmllr.cfg", 40),
+                  ("cfg/TIMIT_baselines/TIMIT_MLP_fmllr.cfg", 440), ("cfg/TIMIT_baselines/TIMIT_SincNet_raw.cfg", 3200),
+                  ("cfg/Librispeech_baselines/libri_GRU_fmllr.cfg", 40)]
+
+
+def _is_orthogonal(v):
+    if v.dim() != 2 or not v.is_floating_point() or min(v.shape) < 2:
+        return False
+    w = v.double()
+    g = w @ w.t() if w.shape[0] <= w.shape[1] else w.t() @ w
+    return bool(torch.allclose(g, torch.eye(g.shape[0], dtype=torch.float64), atol=1e-5))
+
+
+def _fingerprint(v):
+    w = v.double().reshape(-1)
+    idx = torch.linspace(0, w.numel() - 1, 64).long()
+    return {"sum": float(w.sum()), "sumsq": float((w * w).sum()), "idx": idx.tolist(), "values": w[idx].tolist()}
+
+
+def dropin_case(name):
+    """What the reference's own caller builds from the shipped cfg files (utils.model_init + optimizer_init with the
+    reference's neural_networks, seed 1234, the cfg's output sizes 1938 / 48): network and cost order, every out_dim,
+    parameter and state_dict entries with shape, dtype and the SHA-256 of their initial values, optimizer type and
+    param_groups - plus the cfg file itself.  Pins tests/test_dropin_reference.py."""
+    import hashlib
+
+    import utils as ref_utils  # the reference's
+
+    out = {}
+    for rel, feat_dim in DROPIN_RECIPES:
+        text = open(os.path.join(REF, rel)).read()
+        cfg = configparser.ConfigParser()
+        cfg.read_string(text)
+        cfg["exp"]["to_do"], cfg["exp"]["use_cuda"] = "train", "False"
+        n_out = {"N_out_lab_cd": 1938, "N_out_lab_mono": 48}
+        arch_dict = {}
+        for sec in cfg.sections():
+            if sec.startswith("architecture"):
+                for k, v in cfg[sec].items():
+                    if v in n_out:
+                        cfg[sec][k] = str(n_out[v])
+                arch_dict[cfg[sec]["arch_name"]] = [sec, cfg[sec]["arch_name"], bool(ref_utils.strtobool(cfg[sec]["arch_seq_model"]))]
+        model = cfg["model"]["model"].split("\n")
+        fea = [ln for ln in model if "compute" in ln][0].split(",")[1].strip(" )")
+        iod = {fea: [0, feat_dim, feat_dim]}
+        torch.manual_seed(1234)
+        nns, costs = ref_utils.model_init(iod, model, cfg, arch_dict, False, False, "train")
+        opts = ref_utils.optimizer_init(nns, cfg, arch_dict)
+        nets = {}
+        for k, net in nns.items():
+            sd = net.state_dict()
+            nets[k] = {"class": type(net).__name__, "out_dim": int(net.out_dim), "training": net.training,
+                       "parameters": [n for n, _ in net.named_parameters()],
+                       "state_dict": [[n, list(v.shape), str(v.dtype),
+                                       hashlib.sha256(v.detach().contiguous().numpy().tobytes()).hexdigest()]
+                                      for n, v in sd.items()],
+                       # orthogonal initialisations go through LAPACK's QR, whose last bits differ between CPU builds:
+                       # their sum, sum of squares and 64 fixed elements, for hosts whose bits differ from these
+                       "orthogonal": {n: _fingerprint(v) for n, v in sd.items() if _is_orthogonal(v)},
+                       "optimizer": type(opts[k]).__name__,
+                       "param_groups": opts[k].state_dict()["param_groups"]}
+        out[rel] = {"cfg": text, "feat_dim": feat_dim, "nns": list(nns), "costs": list(costs), "inp_out_dict": iod,
+                    "nets": nets}
+    path = os.path.join(OUT, name + ".json")
+    with open(path, "w") as f:
+        json.dump(out, f, indent=1, sort_keys=True)
+    print("wrote %s (%d bytes)" % (path, os.path.getsize(path)))
+
+
+def interface_case(name):
+    """The functions of the reference's core.py (name -> parameter names), read from its source without importing it:
+    what tests/test_host_logic_round6.py gives the stub checkout its launcher and core shim are run against."""
+    import ast
+
+    src = open(os.path.join(REF, "core.py")).read()
+    funcs = {n.name: [a.arg for a in n.args.args] for n in ast.parse(src).body if isinstance(n, ast.FunctionDef)}
+    path = os.path.join(OUT, name + ".json")
+    with open(path, "w") as f:
+        json.dump({"core.py": funcs}, f, indent=1, sort_keys=True)
+    print("wrote %s (%d bytes)" % (path, os.path.getsize(path)))
+
+
 def main():
     torch.set_num_threads(1)  # bit-stable fixtures
     if os.environ.get("PK_GOLDEN_ONLY") == "chunk":  # regenerate only the chunk-loop fixture
@@ -980,6 +1062,12 @@ def main():
         return
     if os.environ.get("PK_GOLDEN_ONLY") == "cfg":
         cfg_case("cfg_recipes")
+        return
+    if os.environ.get("PK_GOLDEN_ONLY") == "dropin":
+        dropin_case("dropin_model_init")
+        return
+    if os.environ.get("PK_GOLDEN_ONLY") == "interface":
+        interface_case("ref_core_interface")
         return
     if os.environ.get("PK_GOLDEN_ONLY") == "io":
         io_case("io_kaldi_tables", 77)
@@ -1073,6 +1161,8 @@ def main():
     loader_case("io_chunk_loader", 91)
     reader_case("io_chunk_reader", 57)
     cfg_case("cfg_recipes")
+    interface_case("ref_core_interface")
+    dropin_case("dropin_model_init")
 
 
 if __name__ == "__main__":

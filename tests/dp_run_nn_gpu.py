@@ -1,6 +1,6 @@
 """Worker of tests/test_gpu_dp_run_nn.py: core.run_nn_dp itself on N ranks of ONE GPU (gloo over device tensors - RCCL
-refuses several ranks per device), strong-scaling shapes: a global batch of 128 sequences, every rank keeps 128 / N
-columns (N = 8: 16 sequences = 32 rows = two-cluster persistent launches).
+refuses several ranks per device), strong-scaling shapes: a global batch of --batch sequences (128 by default), every rank
+keeps batch / N columns (N = 4, batch 64: 16 sequences = 32 rows = two-cluster persistent launches).
 
 --reference: one process that replays the same chunk the N-GPU parity definition's way: every batch, every
 shard in turn from the same parameters and running statistics, gradients averaged, rank 0's running statistics kept,
@@ -64,13 +64,17 @@ def write_cfg(rcp, tmp):
 
 
 def main():
+    global B
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", required=True)
     ap.add_argument("--tmp", required=True)
     ap.add_argument("--prec", default="bf16")
-    ap.add_argument("--world", type=int, default=8)
+    ap.add_argument("--world", type=int, default=4)
+    ap.add_argument("--batch", type=int, default=B, help="global batch (sequences), split evenly over the ranks")
     ap.add_argument("--reference", action="store_true")
     a = ap.parse_args()
+    B = a.batch
+    assert B % a.world == 0, (B, a.world)
     F_ = importlib.import_module("pytorch-kaldi_amd.functional")
     core = importlib.import_module("pytorch-kaldi_amd.core")
     _lib = importlib.import_module("pytorch-kaldi_amd._lib")

@@ -75,6 +75,8 @@ def test_bench_starts_its_own_ranks():
     import sys
 
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    # the CPU path on every host: with one GPU visible both ranks would land on it, and RCCL refuses two ranks per device
+    env.update(HIP_VISIBLE_DEVICES="-1", CUDA_VISIBLE_DEVICES="-1")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--launch-check"], env=env,
                        stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
@@ -173,3 +175,63 @@ def test_round6_line_is_complete_per_configuration():
     assert len(pb["chunks_s"]) >= 2
     dc = json.load(open(os.path.join(ROOT, "profiles", "r06_driver_cmd.json")))
     assert dc["first_process"]["steps"] == 20 and dc["first_process"]["warmup"] == 5 and dc["first_process"]["ms_per_step"] < 17.5
+
+
+def _bench_module():
+    import importlib.util
+
+    spec = importlib.util.spec_from_file_location("_bench_under_test", os.path.join(ROOT, "bench.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+def test_dump_outputs_writes_the_last_step_within_the_budget(tmp_path):
+    """--dump-outputs: every value the model lines define and every parameter / floating buffer, as <name>.npy in float32
+    (float64 kept), at most 64 MB in all; an array too large for the budget becomes a sample at the same positions in every
+    run, so that two runs (two builds) compare element for element."""
+    import types
+
+    import numpy as np
+    import torch
+
+    bench = _bench_module()
+    g = torch.Generator().manual_seed(0)
+    head = torch.nn.Linear(8, 5)
+    bn = torch.nn.BatchNorm1d(5)
+    outs = {"fea": torch.randn(4, 8, generator=g),                               # an input slice: not a model line's value
+            "out_dnn1": torch.randn(24_000_000, generator=g).reshape(-1, 1000),  # 96 MB: over the budget on its own
+            "out_dnn2": torch.randn(6, 5, generator=g).to(torch.bfloat16),
+            "loss_final": torch.tensor(2.5, dtype=torch.float64),
+            "err_final": torch.tensor(0.75)}
+    tr = types.SimpleNamespace(rcp={"model": ["out_dnn1=compute(A,fea)", "out_dnn2=compute(B,out_dnn1)",
+                                              "loss_final=cost_nll(out_dnn2,lab_cd)", "err_final=cost_err(out_dnn2,lab_cd)"]},
+                               last_outs=outs, nns={"MLP_layers": torch.nn.Sequential(head, bn)})
+    rec = bench.dump_outputs(tr, str(tmp_path / "a"))
+    names = sorted(f[:-4] for f in os.listdir(tmp_path / "a"))
+    assert names == sorted(["out_dnn1", "out_dnn2", "loss_final", "err_final", "param.MLP_layers.0.weight",
+                            "param.MLP_layers.0.bias", "param.MLP_layers.1.weight", "param.MLP_layers.1.bias",
+                            "buffer.MLP_layers.1.running_mean", "buffer.MLP_layers.1.running_var"])
+    assert rec["files"] == len(names) and rec["sampled"] == ["out_dnn1"]
+    total = sum(os.path.getsize(os.path.join(tmp_path / "a", f)) for f in os.listdir(tmp_path / "a"))
+    assert total <= 64 << 20 and rec["bytes"] <= total
+    loaded = {n: np.load(os.path.join(tmp_path / "a", n + ".npy")) for n in names}
+    assert loaded["loss_final"].dtype == np.float64 and float(loaded["loss_final"]) == 2.5
+    assert all(v.dtype == np.float32 for n, v in loaded.items() if n != "loss_final")
+    assert np.array_equal(loaded["out_dnn2"], outs["out_dnn2"].float().numpy())
+    assert np.array_equal(loaded["param.MLP_layers.0.weight"], head.weight.detach().numpy())
+    s = loaded["out_dnn1"]
+    assert s.ndim == 1 and 1_000_000 < s.size < outs["out_dnn1"].numel()
+    assert np.isin(s[:1000], outs["out_dnn1"].reshape(-1).numpy()).all()   # a sample of the array's own elements
+    bench.dump_outputs(tr, str(tmp_path / "b"))
+    for n in names:
+        assert np.array_equal(loaded[n], np.load(os.path.join(tmp_path / "b", n + ".npy"))), n
+
+
+def test_bench_rejects_a_step_count_it_cannot_time():
+    import subprocess
+    import sys
+
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], stdout=subprocess.PIPE,
+                       stderr=subprocess.PIPE, text=True, timeout=300)
+    assert r.returncode == 2 and "--steps" in r.stderr

@@ -1,45 +1,39 @@
-"""The drop-in, driven by the REFERENCE's own caller (build container only: /root/reference does not travel).
+"""The drop-in, checked against what the REFERENCE's own caller builds.
 
-A PyTorch-Kaldi user switches engines by editing one cfg line per architecture (arch_library).  Everything that then
-touches the classes is the reference's code, not this package's mirror of it: utils.model_init instantiates
-``arch_class(options, inp_dim)`` through importlib (utils.py:2047-2057), utils.optimizer_init builds torch optimizers
-over ``.parameters()`` (utils.py:2106-2164), core.run_nn loads the previous chunk's ``.pkl`` into both
-(core.py:523-535).  These tests run exactly those functions, imported from /root/reference unmodified, on the shipped
-cfg files with ``arch_library = pytorch-kaldi_amd.nn``.
+A PyTorch-Kaldi user switches engines by editing one cfg line per architecture (arch_library).  The caller then
+instantiates ``arch_class(options, inp_dim)`` through importlib (utils.model_init, utils.py:2047-2057), builds torch
+optimizers over ``.parameters()`` (utils.optimizer_init, utils.py:2106-2164) and loads the previous chunk's ``.pkl`` into
+both (core.py:523-535).  tests/golden/dropin_model_init.json holds what the reference's model_init + optimizer_init built
+from the shipped cfg files with its own neural_networks (oracle/make_golden.py::dropin_case: every name, out_dim, shape,
+dtype, optimizer group and the SHA-256 of every initial value at seed 1234 - with a float64 fingerprint of the
+orthogonally initialised matrices, whose LAPACK QR may round differently on another host) and the cfg files themselves; these tests run
+the package's model_init / optimizer_init (pytorch-kaldi_amd/utils.py, the same importlib dispatch) on those cfg files
+with ``arch_library = pytorch-kaldi_amd.nn`` and require the same result.
 """
 import configparser
+import hashlib
 import importlib
+import json
 import os
-import sys
 
 import pytest
 import torch
 
 from golden_util import Golden
 
-REF = os.environ.get("PK_REFERENCE", "/root/reference")
-pytestmark = pytest.mark.skipif(not os.path.exists(os.path.join(REF, "utils.py")),
-                                reason="needs the reference checkout (build container only)")
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+GOLD = json.load(open(os.path.join(ROOT, "tests", "golden", "dropin_model_init.json")))
 
 
 @pytest.fixture(scope="module")
 def ref_utils():
-    sys.dont_write_bytecode = True
-    sys.path.insert(0, REF)
-    saved = sys.modules.pop("utils", None), sys.modules.pop("data_io", None)
-    try:
-        yield importlib.import_module("utils")
-    finally:
-        sys.path.remove(REF)
-        for name, mod in zip(("utils", "data_io"), saved):
-            sys.modules.pop(name, None)
-            if mod is not None:
-                sys.modules[name] = mod
+    """The caller: the package's model_init / optimizer_init (they dispatch on arch_library as the reference's do)."""
+    return importlib.import_module("pytorch-kaldi_amd.utils")
 
 
-def _cfg(path, library, n_out):
+def _cfg(text, library, n_out):
     cfg = configparser.ConfigParser()
-    cfg.read(os.path.join(REF, path))
+    cfg.read_string(text)
     cfg["exp"]["to_do"] = "train"
     cfg["exp"]["use_cuda"] = "False"  # construction only: the engine's forward needs the GPU
     for sec in cfg.sections():
@@ -62,7 +56,7 @@ RECIPES = [
 
 def _build(ref_utils, path, library, feat_dim):
     n_out = {"N_out_lab_cd": 1938, "N_out_lab_mono": 48}
-    cfg = _cfg(path, library, n_out)
+    cfg = _cfg(GOLD[path]["cfg"], library, n_out)
     model = cfg["model"]["model"].split("\n")
     arch_dict = {}
     for sec in cfg.sections():
@@ -75,45 +69,60 @@ def _build(ref_utils, path, library, feat_dim):
     return cfg, nns, costs, opts, inp_out_dict
 
 
+def _sha(t):
+    return hashlib.sha256(t.detach().contiguous().numpy().tobytes()).hexdigest()
+
+
 @pytest.mark.parametrize("path,feat_dim", RECIPES)
 def test_reference_model_init_builds_the_engine_classes(ref_utils, path, feat_dim):
-    """utils.model_init + optimizer_init of the reference on the SHIPPED cfg with arch_library switched: same
-    architectures, out_dims, parameter names / shapes / order, optimizer types and hyper-parameters as with the
+    """model_init + optimizer_init on the SHIPPED cfg with arch_library switched: same architectures, out_dims,
+    parameter names / shapes / order, optimizer types and hyper-parameters as the reference's caller built with the
     reference's own neural_networks - and, with the same seed, the same initial weights."""
     nn_amd = importlib.import_module("pytorch-kaldi_amd.nn")
-    torch.manual_seed(1234)
-    _, nns_e, costs_e, opts_e, iod_e = _build(ref_utils, path, "pytorch-kaldi_amd.nn", feat_dim)
-    torch.manual_seed(1234)
-    _, nns_r, costs_r, opts_r, iod_r = _build(ref_utils, path, "neural_networks", feat_dim)
-    assert list(nns_e) == list(nns_r) and list(costs_e) == list(costs_r)
-    assert iod_e == iod_r  # every out_dim the interpreter derived
-    for name in nns_r:
-        e, r = nns_e[name], nns_r[name]
-        assert type(e).__module__ == nn_amd.__name__ and type(e).__name__ == type(r).__name__
-        assert e.out_dim == r.out_dim and e.training == r.training
-        pe, pr = list(e.named_parameters()), list(r.named_parameters())
-        assert [k for k, _ in pe] == [k for k, _ in pr]  # the order indexes torch optimizer state
-        sde, sdr = e.state_dict(), r.state_dict()
-        assert list(sde) == list(sdr)
-        for k in sdr:
-            assert sde[k].shape == sdr[k].shape and sde[k].dtype == sdr[k].dtype, (name, k)
-            assert torch.equal(sde[k], sdr[k]), (name, k)  # same seed -> same initialisation
-        assert type(opts_e[name]) is type(opts_r[name])
-        ge, gr = opts_e[name].state_dict()["param_groups"], opts_r[name].state_dict()["param_groups"]
-        assert ge == gr
-        # a reference-written checkpoint of this architecture loads into the engine's module and its optimizer
-        ck = {"model_par": r.state_dict(), "optimizer_par": opts_r[name].state_dict()}
+    want = GOLD[path]
+    assert want["feat_dim"] == feat_dim
+    threads = torch.get_num_threads()
+    torch.set_num_threads(1)  # (as the fixture was recorded: the orthogonal initialisation's QR, bit for bit)
+    try:
+        torch.manual_seed(1234)
+        _, nns_e, costs_e, opts_e, iod_e = _build(ref_utils, path, "pytorch-kaldi_amd.nn", feat_dim)
+    finally:
+        torch.set_num_threads(threads)
+    assert list(nns_e) == want["nns"] and list(costs_e) == want["costs"]
+    assert {k: list(v) for k, v in iod_e.items()} == want["inp_out_dict"]  # every out_dim the interpreter derived
+    for name, r in want["nets"].items():
+        e = nns_e[name]
+        assert type(e).__module__ == nn_amd.__name__ and type(e).__name__ == r["class"]
+        assert e.out_dim == r["out_dim"] and e.training == r["training"]
+        assert [k for k, _ in e.named_parameters()] == r["parameters"]  # the order indexes torch optimizer state
+        sde = e.state_dict()
+        assert list(sde) == [k for k, _, _, _ in r["state_dict"]]
+        for k, shape, dtype, sha in r["state_dict"]:
+            assert list(sde[k].shape) == shape and str(sde[k].dtype) == dtype, (name, k)
+            if _sha(sde[k]) != sha:  # same seed -> same initialisation
+                # (only where LAPACK's QR is involved may another host's last bits differ from the recorded ones)
+                fp = r["orthogonal"].get(k)
+                assert fp is not None, (name, k)
+                # (fp32 QR rounding: up to ~2e-6 per element, of either sign - a sum of n of them grows as sqrt(n))
+                w = sde[k].double().reshape(-1)
+                assert abs(float(w.sum()) - fp["sum"]) < 1e-5 * w.numel() ** 0.5, (name, k)
+                assert abs(float((w * w).sum()) - fp["sumsq"]) < 1e-5 * fp["sumsq"], (name, k)
+                assert torch.allclose(w[fp["idx"]], torch.tensor(fp["values"], dtype=torch.float64), rtol=1e-5, atol=1e-5), (name, k)
+        assert type(opts_e[name]).__name__ == r["optimizer"] and type(opts_e[name]).__module__.startswith("torch.optim")
+        assert json.loads(json.dumps(opts_e[name].state_dict()["param_groups"])) == r["param_groups"]
+        # a checkpoint of this architecture in the reference's layout loads into the engine's module and its optimizer
+        ck = {"model_par": {k: v.clone() for k, v in sde.items()}, "optimizer_par": opts_e[name].state_dict()}
         e.load_state_dict(ck["model_par"])
         opts_e[name].load_state_dict(ck["optimizer_par"])
 
 
-def test_reference_written_checkpoint_loads_through_the_reference_caller(ref_utils):
+def test_reference_written_checkpoint_loads_through_the_reference_caller(ref_utils, tmp_path):
     """core.py:523-535 with a REAL reference checkpoint: tests/golden/chunk_ligru_run_nn.npz holds the .pkl contents
     the reference's run_nn wrote after its first training chunk (model_par + RMSprop state after several steps)."""
     g = Golden("chunk_ligru_run_nn")
     m = g.meta
     cfg = configparser.ConfigParser()
-    cfg.read_string(m["cfgs"]["ck1"].replace("{OUT}", "/tmp"))
+    cfg.read_string(m["cfgs"]["ck1"].replace("{OUT}", str(tmp_path)))
     arch_dict = m["arch_dict"]
     for sec in ("architecture1", "architecture2", "architecture3"):
         cfg[sec]["arch_library"] = "pytorch-kaldi_amd.nn"

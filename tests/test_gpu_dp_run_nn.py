@@ -1,5 +1,6 @@
-"""core.run_nn_dp on EIGHT ranks of one GPU, strong-scaling shapes (global batch 128 -> 16 sequences = 32 rows per rank:
-two-cluster persistent launches, eight processes' kernels sharing the chip), against a one-process replay of the same chunk
+"""core.run_nn_dp on four ranks of one GPU, strong-scaling shapes (global batch 64 -> 16 sequences = 32 rows per rank:
+two-cluster persistent launches, four processes' kernels sharing the chip; at most six processes hold the GPU at once:
+pytest, the launcher and the ranks), against a one-process replay of the same chunk
 shard by shard with averaged gradients (the N-GPU parity definition of SURVEY.md 8e; the reference's own multi-GPU hook is
 core.py:103-104, 537-538).  Transport: gloo over device tensors (RCCL refuses several ranks per device); every kernel,
 stream, bucket and the chunk loop's own plumbing - column assignment, reducer over the fused optimizers' flat buckets, rank
@@ -25,15 +26,16 @@ def _free_port():
     return p
 
 
-@pytest.mark.parametrize("world,prec", [(8, "bf16"), (4, "fp32")])
-def test_run_nn_dp_on_n_ranks_of_one_gpu_equals_the_shard_average(tmp_path, world, prec):
+@pytest.mark.parametrize("world,prec,batch", [(4, "bf16", 64), (4, "fp32", 128)], ids=["4-bf16", "4-fp32"])
+def test_run_nn_dp_on_n_ranks_of_one_gpu_equals_the_shard_average(tmp_path, world, prec, batch):
     ref_out, dp_out = str(tmp_path / "ref.pt"), str(tmp_path / "dp.pt")
     env = dict(os.environ, OMP_NUM_THREADS="1", HSA_ENABLE_IPC_MODE_LEGACY="0")  # (same thread count as torchrun's workers: LAPACK QR of the orthogonal init)
     r = subprocess.run([sys.executable, WORKER, "--reference", "--out", ref_out, "--tmp", str(tmp_path), "--prec", prec,
-                        "--world", str(world)], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=600, env=env)
+                        "--world", str(world), "--batch", str(batch)], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=600, env=env)
     assert r.returncode == 0, r.stdout[-3000:]
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(world), "--master-addr", "127.0.0.1",
-           "--master-port", str(_free_port()), WORKER, "--out", dp_out, "--tmp", str(tmp_path), "--prec", prec, "--world", str(world)]
+           "--master-port", str(_free_port()), WORKER, "--out", dp_out, "--tmp", str(tmp_path), "--prec", prec, "--world", str(world),
+           "--batch", str(batch)]
     r = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-4000:]
     ref, got = torch.load(ref_out), torch.load(dp_out)

@@ -1,6 +1,11 @@
 """Host-side logic added in round 6 (runs without a GPU): the shipped ``core`` shim resolved the way run_exp.py resolves
-it, the gradient wire's default, the reducer's reset after a step that did not complete."""
+it, the gradient wire's default, the reducer's reset after a step that did not complete.
+
+The shim is run against a stand-in PyTorch-Kaldi checkout written into a temporary directory: a ``run_exp.py`` and a
+``core.py`` whose functions carry the names and parameter lists of the reference's core.py
+(tests/golden/ref_core_interface.json, recorded by oracle/make_golden.py::interface_case)."""
 import importlib
+import json
 import os
 import subprocess
 import sys
@@ -10,13 +15,24 @@ import pytest
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF = os.environ.get("PK_REFERENCE", "/root/reference")
 core = importlib.import_module("pytorch-kaldi_amd.core")
 dp = importlib.import_module("pytorch-kaldi_amd.dp")
 F_ = importlib.import_module("pytorch-kaldi_amd.functional")
 
-needs_reference = pytest.mark.skipif(not os.path.isfile(os.path.join(REF, "run_exp.py")),
-                                     reason="no PyTorch-Kaldi checkout here (the GPU box has none)")
+
+
+@pytest.fixture
+def checkout(tmp_path):
+    """A stand-in checkout: run_exp.py (the probes below replace it) and a core.py with the reference's functions."""
+    root = tmp_path / "pytorch-kaldi"
+    root.mkdir()
+    funcs = json.load(open(os.path.join(ROOT, "tests", "golden", "ref_core_interface.json")))["core.py"]
+    src = ['"""Stand-in for a PyTorch-Kaldi checkout\'s core.py: its functions by name and parameter list."""\n']
+    for name, params in sorted(funcs.items()):
+        src.append("\n\ndef %s(%s):\n    raise NotImplementedError(%r)\n" % (name, ", ".join(params), name))
+    (root / "core.py").write_text("".join(src))
+    (root / "run_exp.py").write_text('raise SystemExit("stand-in checkout: run_exp.py needs Kaldi data")\n')
+    return str(root)
 
 RUN_EXP_LINES = """
 import importlib
@@ -27,7 +43,7 @@ run_nn = getattr(module, run_nn_script)
 """
 
 
-def _as_run_exp_does(script, body, tmp_path, **env_extra):
+def _as_run_exp_does(script, body, tmp_path, ref, **env_extra):
     """integration/run_exp_mi355x.py started in the checkout, executing - in place of run_exp.py, which needs Kaldi data -
     a probe that holds the statements of run_exp.py that touch `core` (line 37 and lines 129-131), then `body`."""
     probe = tmp_path / "probe_run_exp.py"
@@ -37,14 +53,13 @@ def _as_run_exp_does(script, body, tmp_path, **env_extra):
     env.pop("PYTHONPATH", None)
     env.update(env_extra)
     r = subprocess.run([sys.executable, "-W", "ignore", os.path.join(ROOT, "integration", "run_exp_mi355x.py"), "cfg/x.cfg"],
-                       cwd=REF, env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=300)
+                       cwd=ref, env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=300)
     assert r.returncode == 0, r.stdout[-3000:]
     return r.stdout
 
 
-@needs_reference
 @pytest.mark.parametrize("script", ["run_nn", "run_nn.py", "run_nn_dp"])
-def test_core_shim_resolves_like_run_exp(script, tmp_path):
+def test_core_shim_resolves_like_run_exp(script, tmp_path, checkout):
     """run_exp.py:129-131 (importlib.import_module("core"), getattr(module, run_nn_script)) and :37 (three helpers imported
     from core) against integration/core.py: the chunk function is the engine's, with the reference's parameter list, and
     the helpers are the reference's own objects."""
@@ -61,16 +76,15 @@ def test_core_shim_resolves_like_run_exp(script, tmp_path):
         import sys
         assert sys.argv[1:] == ["cfg/x.cfg"]                    # the command line reaches run_exp.py unchanged
         print("resolved", run_nn.__name__, ref.__file__)
-    """, tmp_path)
-    assert "resolved run_nn_dp " + os.path.join(REF, "core.py") in out
+    """, tmp_path, checkout)
+    assert "resolved run_nn_dp " + os.path.join(checkout, "core.py") in out
 
 
-@needs_reference
-def test_core_shim_passes_through_when_switched_off(tmp_path):
+def test_core_shim_passes_through_when_switched_off(tmp_path, checkout):
     out = _as_run_exp_does("run_nn", """
         assert run_nn is module.reference_core.run_nn and not hasattr(module, "run_nn_dp")
         print("reference", run_nn.__module__)
-    """, tmp_path, PK_CORE_ENGINE="0")
+    """, tmp_path, checkout, PK_CORE_ENGINE="0")
     assert "reference _pk_reference_core" in out
 
 
@@ -82,14 +96,13 @@ def test_launcher_says_what_it_needs_without_a_checkout(tmp_path):
     assert r.returncode != 0 and "PK_KALDI_ROOT" in r.stdout
 
 
-@needs_reference
-def test_pythonpath_alone_does_not_reach_the_shim():
+def test_pythonpath_alone_does_not_reach_the_shim(checkout):
     """Why there is a launcher: with the shim only on PYTHONPATH, `python run_exp.py` (script directory first on
     sys.path) still imports the checkout's own core.py."""
     env = dict(os.environ, PYTHONPATH=os.pathsep.join([os.path.join(ROOT, "integration"), ROOT]))
-    r = subprocess.run([sys.executable, "-W", "ignore", "-c", "import core; print(core.__file__)"], cwd=REF, env=env,
+    r = subprocess.run([sys.executable, "-W", "ignore", "-c", "import core; print(core.__file__)"], cwd=checkout, env=env,
                        stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=300)
-    assert r.returncode == 0 and r.stdout.strip().endswith(os.path.join(REF, "core.py")), r.stdout[-2000:]
+    assert r.returncode == 0 and r.stdout.strip().endswith(os.path.join(checkout, "core.py")), r.stdout[-2000:]
 
 
 def test_gradient_wire_default_follows_the_precision(monkeypatch):
