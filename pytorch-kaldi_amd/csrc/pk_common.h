@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
+#include <stdlib.h>
 
 #include "../../include/pk_amd.h"
 
@@ -11,6 +12,20 @@ void pk_set_error(const char* fmt, ...);
 // A/B levers of past experiments live behind ONE environment variable, PK_EXPERIMENT="key=value,key=value" (pk_lib.hip;
 // the keys are listed in INTEGRATION.md): value of `key`, or nullptr.  Callers cache what they read.
 const char* pk_experiment(const char* key);
+// An integer switch, read once per process:  static const int cap = pk_experiment_int("rec_clusters", 0);
+// (a function-local static is initialised exactly once, also with several host threads)
+inline int pk_experiment_int(const char* key, int dflt) {
+    const char* e = pk_experiment(key);
+    return e ? atoi(e) : dflt;
+}
+// ... and one that is told by its first character: a digit lo .. hi, anything else (or unset) gives dflt
+inline int pk_experiment_digit(const char* key, int lo, int hi, int dflt) {
+    const char* e = pk_experiment(key);
+    return (e && e[0] >= '0' + lo && e[0] <= '0' + hi) ? e[0] - '0' : dflt;
+}
+// Dynamic LDS above the 64 KB default needs an opt-in per kernel, and hipFuncSetAttribute is slow (milliseconds): one
+// cache for the whole library (pk_lib.hip), keyed by the kernel's address, of the largest size granted so far.
+int pk_grant_dynamic_lds(const void* kernel, size_t bytes);
 
 #define PK_CHECK_HIP(expr)                                                                  \
     do {                                                                                    \

@@ -3,6 +3,9 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <mutex>
+#include <unordered_map>
+
 #include "pk_common.h"
 
 static thread_local char g_err[1024] = "";
@@ -38,6 +41,17 @@ const char* pk_experiment(const char* key) {
         p = *end ? end + 1 : end;
     }
     return nullptr;
+}
+
+int pk_grant_dynamic_lds(const void* kernel, size_t bytes) {
+    static std::mutex mu;
+    static std::unordered_map<const void*, size_t> granted;
+    std::lock_guard<std::mutex> lock(mu);
+    size_t& have = granted[kernel];  // (0 for a kernel seen for the first time)
+    if (have >= bytes && have != 0) return 0;
+    PK_CHECK_HIP(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+    have = bytes;
+    return 0;
 }
 
 extern "C" int pk_version(void) { return 100; }

@@ -459,29 +459,50 @@ struct BoolC {  // (an int: 0 = no edge, 1 = even-H edge in 8-byte halves, 2 = o
 
 }  // namespace
 
-// host-side plumbing shared by both translation units (defined in pk_rec_persist2.hip)
+// ---- the host side of every persistent recurrence of these files (defined in pk_rec_persist2.hip).  An entry point
+//   1. checks what is its own (pk_rec2_check, then pitch / alignment / 4 GB range of its exchange buffer),
+//   2. pk_rec2_prepare_{fwd,bwd}: plan, geometry, the pass's fp32 tensors, library scratch and tuning knobs,
+//   3. sets its exchange pointers and the prefill policy,
+//   4. chooses a kernel and its dynamic-LDS size: pk_rec2_run.
+typedef void (*Rec2Kernel)(R2Args);  // every kernel of these files
+typedef int (*Rec2PlanFn)(int R, int H, Plan2& pl);
+// the kernel compiled for this activation: relu, tanh, or the one that takes it at run time
+inline Rec2Kernel pk_rec2_pick_act(int act, Rec2Kernel relu, Rec2Kernel tanh_, Rec2Kernel run_time) {
+    return act == PK_ACT_RELU ? relu : act == PK_ACT_TANH ? tanh_ : run_time;
+}
 int pk_rec2_make_plan(int R, int H, Plan2& pl);
-// per-step LayerNorm (PkLnHost: pk_cell.h)
-int pk_rec2_ln_setup(hipStream_t st, R2Args& a, const Plan2& pl, const PkLnHost* ln, bool backward);  // fills a.ln_*, fills the exchange
-int pk_rec2_ln_finish(hipStream_t st, const R2Args& a, const PkLnHost* ln);  // backward: per-cluster partial sums -> d gamma, d beta
 int pk_rec2_check(const char* who, int cell_ok, int cell, int T, int B, int bidir, int H);
-int pk_rec2_host_setup(R2Args& a, bool backward, int cell);                 // error word, trash page, handshake table, tuning knobs
-int pk_rec2_reset_handshake(hipStream_t st, R2Args& a);  // before every launch: a fresh handshake generation
-// The clusters of a persistent launch exchange h_t with each other every step: every workgroup of the grid has to be
-// resident at the same time.  Checks the grid against what the device can hold (occupancy query for this kernel, block
-// size and dynamic LDS x CU count, cached per kernel) - a grid that cannot be co-resident is refused here instead of
-// ending in bounded-spin time-outs.  (Kernels of OTHER streams or processes can still delay a workgroup's start; that
-// only costs time: every spin is bounded at ~10 ms and reported.)
-int pk_rec2_check_residency(const void* kernel, int threads, size_t lds, int grid, const char* who);
+// a = {} + geometry, plan (made by `plan`: pk_rec2_make_plan, or the fourth generation's own), the forward / backward
+// pointer group, error word, trash page, handshake table, tuning knobs.  pitch: a.Ypitch (forward) / a.Gpitch (backward).
+int pk_rec2_prepare_fwd(R2Args& a, Plan2& pl, Rec2PlanFn plan, int cell, int act, int T, int B, int bidir, int H, int64_t pitch,
+                        const float* P, const float* pscale, const float* pshift, const float* U, const float* mask,
+                        float mask_scalar, float* Y, float* S);
+int pk_rec2_prepare_bwd(R2Args& a, Plan2& pl, Rec2PlanFn plan, int cell, int act, int T, int B, int bidir, int H, int64_t pitch,
+                        const float* U, const float* mask, float mask_scalar, const float* Y, const float* S, const float* dY,
+                        float* dP2);
+int pk_rec2_f32_self_fill();  // PK_EXPERIMENT rec4_self_fill (one switch for both exact-fp32 generations): 0 = one fill in front
+// The launches of one pass: per-step LayerNorm if ln is given (PkLnHost: pk_cell.h; fills a.ln_* and the row-statistics
+// exchange), the grant of the dynamic LDS, then per launch row0 / ln_cg0, a fresh handshake generation, the
+// residency check (every workgroup of a persistent grid has to be resident at the same time: a grid that cannot be is
+// refused instead of ending in bounded-spin time-outs), the L2 run-ahead helpers the policy allows (pk_rec_helper.hip;
+// never with per-step LayerNorm) and the kernel; behind a backward pass with LayerNorm, d gamma / d beta.
+enum Rec2Help {
+    REC2_HELP_NONE,  // no helpers
+    REC2_HELP_FULL,  // what pk_rec_helper_wanted says; S is [ndir][T * B][NS * H] (liGRU / RNN / LSTM)
+    REC2_HELP_PROJ,  // the projections only (forward pass of the two-phase cells, whose S has its own layout)
+};
+int pk_rec2_run(hipStream_t st, R2Args& a, const Plan2& pl, int cell, bool backward, Rec2Kernel k, int threads, size_t lds,
+                const char* who, const PkLnHost* ln, Rec2Help help);
 // third generation (pk_rec_persist3.hip: swapped MFMA operands): the backward pass of liGRU / RNN by default (PK_EXPERIMENT rec_gen*)
 int pk_rec3_covers(int cell, int backward);
-int pk_rec3_launch(hipStream_t st, R2Args& a, const Plan2& pl, int cell, int act, bool backward, bool traced);
+Rec2Kernel pk_rec3_kernel(int cell, int act, bool backward, bool traced, size_t* lds);
 // L2 run-ahead helpers on the idle CUs (pk_rec_helper.hip; PK_REC_HELPER): fork before the recurrence is launched,
 // launch behind it.  They only load - results never depend on them.
 int pk_rec_helper_wanted(bool backward, int launches, int cell);  // -> the mode bits this pass takes (0: none)
 int pk_rec_helper_fork(hipStream_t st);
 int pk_rec_helper_launch(hipStream_t st, const R2Args& a, const Plan2& pl, int G, int NS, bool backward, bool s_layout_ok,
                          int mode);
-// eight-wave LSTM kernels (pk_rec_persist2_lstm.hip): on unless PK_EXPERIMENT lstm_waves=4; the launch loop over pl.launches
+// eight-wave LSTM kernels (pk_rec_persist2_lstm.hip): on unless PK_EXPERIMENT lstm_waves=4.  pk_rec2l_kernel also sets
+// a.helper_delay.
 int pk_rec2l_enabled();
-int pk_rec2l_launch(hipStream_t st, R2Args& a, const Plan2& pl, int act, bool backward);
+Rec2Kernel pk_rec2l_kernel(R2Args& a, int act, bool backward, size_t* lds);

@@ -224,25 +224,26 @@ unsigned g_ticket_row = 0;
 int g_mode = -1, g_lead_p = 3, g_lead_o = 1, g_lead_b = 2, g_hpc = 4, g_delay = 0;
 
 // -1 = PK_REC_HELPER unset: the per-cell default (pk_rec_helper_wanted)
-int helper_mode() {
-    static bool read = false;
-    if (!read) {
-        read = true;
-        const char* e = getenv("PK_REC_HELPER");
-        g_mode = e ? (atoi(e) & 7) : -1;
-        const char* l = pk_experiment("helper_lead");  // "p:o:b": steps ahead for P / the output lines / the backward loads
-        if (l) {
-            int p = 0, o = 0, b = 0;
-            const int n = sscanf(l, "%d:%d:%d", &p, &o, &b);
-            if (n >= 1 && p > 0) g_lead_p = p;
-            if (n >= 2 && o > 0) g_lead_o = o;
-            if (n >= 3 && b > 0) g_lead_b = b;
-        }
-        const char* w = pk_experiment("helper_wgs");  // helper workgroups per cluster
-        if (w && atoi(w) > 0) g_hpc = atoi(w) > 6 ? 6 : atoi(w);
-        const char* d = pk_experiment("helper_delay");  // units of 64 clocks
-        if (d && atoi(d) >= 0) g_delay = atoi(d);
+int read_helper_env() {
+    const char* e = getenv("PK_REC_HELPER");
+    g_mode = e ? (atoi(e) & 7) : -1;
+    const char* l = pk_experiment("helper_lead");  // "p:o:b": steps ahead for P / the output lines / the backward loads
+    if (l) {
+        int p = 0, o = 0, b = 0;
+        const int n = sscanf(l, "%d:%d:%d", &p, &o, &b);
+        if (n >= 1 && p > 0) g_lead_p = p;
+        if (n >= 2 && o > 0) g_lead_o = o;
+        if (n >= 3 && b > 0) g_lead_b = b;
     }
+    const int w = pk_experiment_int("helper_wgs", 0);  // helper workgroups per cluster
+    if (w > 0) g_hpc = w > 6 ? 6 : w;
+    const int d = pk_experiment_int("helper_delay", -1);  // units of 64 clocks
+    if (d >= 0) g_delay = d;
+    return 0;
+}
+int helper_mode() {
+    static const int once = read_helper_env();  // (the environment gives the starting values; pk_rec_helper_set_mode changes them)
+    (void)once;
     return g_mode;
 }
 int ensure_helper() {
@@ -251,8 +252,7 @@ int ensure_helper() {
     PK_CHECK_HIP(hipEventCreateWithFlags(&g_fork, hipEventDisableTiming));
     PK_CHECK_HIP(hipEventCreateWithFlags(&g_join, hipEventDisableTiming));
     PK_CHECK_HIP(hipMalloc((void**)&g_tickets, 64 * 8 * sizeof(unsigned) + 64));
-    PK_CHECK_HIP(hipFuncSetAttribute((const void*)rec_helper_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, HELPER_LDS));
-    return 0;
+    return pk_grant_dynamic_lds((const void*)rec_helper_kernel, HELPER_LDS);
 }
 
 }  // namespace

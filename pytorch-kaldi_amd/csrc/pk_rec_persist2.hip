@@ -738,11 +738,7 @@ int pk_rec2_make_plan(int R, int H, Plan2& pl) {
         // rows as for 16, and the CUs left over go to the weight-gradient GEMMs of the side stream (256 rows: 16 clusters
         // instead of 24, 19.09 -> 18.99 ms per step; a count that is not a multiple of 8 straddles XCDs: 23.6 ms).
         // PK_EXPERIMENT rec_clusters overrides the cap.
-        static int cap = -1;
-        if (cap < 0) {
-            const char* e = pk_experiment("rec_clusters");
-            cap = e ? atoi(e) : 0;
-        }
+        static const int cap = pk_experiment_int("rec_clusters", 0);
         const int full = (((R + RMAX - 1) / RMAX) + 7) & ~7;
         const int want = cap > 0 ? cap : full;
         if (want < C) C = want;
@@ -776,7 +772,7 @@ extern "C" int64_t pk_rec_ln_work_floats(int T, int B, int bidir, int H) {
     const int64_t gen4 = pk_rec4f_ln_work_floats(T, B, bidir, H);  // (the caller does not say which kernels will run)
     return gen2 > gen4 ? gen2 : gen4;
 }
-int pk_rec2_ln_setup(hipStream_t st, R2Args& a, const Plan2& pl, const PkLnHost* ln, bool backward) {
+static int pk_rec2_ln_setup(hipStream_t st, R2Args& a, const Plan2& pl, const PkLnHost* ln, bool backward) {
     a.ln_gamma = a.ln_beta = nullptr;
     a.lnh = a.lnstat = a.lnx = a.lnpart = nullptr;
     a.ln_eps = 0.f; a.ln_cg0 = 0; a.ln_ncg = 0;
@@ -797,7 +793,7 @@ int pk_rec2_ln_setup(hipStream_t st, R2Args& a, const Plan2& pl, const PkLnHost*
     if (backward) PK_CHECK_HIP(hipMemsetAsync(a.lnpart, 0, (size_t)2 * a.ln_ncg * KPAD * 4, st));  // clusters without rows add nothing
     return 0;
 }
-int pk_rec2_ln_finish(hipStream_t st, const R2Args& a, const PkLnHost* ln) {
+static int pk_rec2_ln_finish(hipStream_t st, const R2Args& a, const PkLnHost* ln) {
     if (ln == nullptr) return 0;
     float* part = a.lnpart + (size_t)2 * a.ln_ncg * KPAD;
     int rc = pk_colsum((void*)st, a.lnpart, nullptr, KPAD, a.ln_ncg, a.H, part, ln->dgamma);
@@ -818,12 +814,8 @@ int pk_rec2_check(const char* who, int cell_ok, int cell, int T, int B, int bidi
 // with the dword-level test a re-poll is cheap and the DELAY sweep of tools/trace_rec2.py (Li-GRU, BASELINE geometry) is
 // flat between 0 and 2 units (forward 5160-5200, backward 5750-5870 clocks per step) and rises beyond.
 static int default_poll_delay(bool backward, int cell) {
-    static int env[2] = {-2, -2};
-    int& e = env[backward ? 1 : 0];
-    if (e == -2) {
-        const char* v = pk_experiment(backward ? "poll_delay_bwd" : "poll_delay_fwd");
-        e = v ? atoi(v) : -1;
-    }
+    static const int env[2] = {pk_experiment_int("poll_delay_fwd", -1), pk_experiment_int("poll_delay_bwd", -1)};
+    const int e = env[backward ? 1 : 0];
     if (e >= 0) return e;
     // Per cell and pass.  Li-GRU (end of round 2, 16 clusters + self-filling exchange, whole training step on one box):
     // backward 1 -> 18.47 ms, 0 -> 18.36, 2 -> 18.24; forward 1 vs 2: 18.45 vs 18.47.  The eight-wave LSTM backward polls
@@ -835,7 +827,8 @@ static int default_poll_delay(bool backward, int cell) {
     return 2;
 }
 
-int pk_rec2_host_setup(R2Args& a, bool backward, int cell) {
+// error word, trash page, handshake table, tuning knobs
+static int pk_rec2_host_setup(R2Args& a, bool backward, int cell) {
     int rc = ensure_err2();
     if (rc) return rc;
     a.err = g2_err_dev; a.spin_limit = 400000; a.trace = g2_trace; a.xcd_tab = g2_xcd_tab; a.force_safe = g2_force_safe;
@@ -843,18 +836,50 @@ int pk_rec2_host_setup(R2Args& a, bool backward, int cell) {
     a.helper_delay = 0;
     a.empty_step = g2_empty_step;
     a.self_fill = 0;
-    {   // PK_EXPERIMENT rec_flush_late=1: the third-generation kernels issue a step's output stores / next-step loads behind its MFMA
-        // block instead of right behind the barrier (A/B switch)
-        static int fl = -1;
-        if (fl < 0) {
-            const char* e = pk_experiment("rec_flush_late");
-            fl = e ? atoi(e) : 0;  // (third generation: 1 = late; role-split kernels: bit 0 no priorities, bit 1 nt stores, bit 2 nt loads)
-        }
-        a.flush_late = fl;
-    }
+    // PK_EXPERIMENT rec_flush_late=1: the third-generation kernels issue a step's output stores / next-step loads behind its MFMA
+    // block instead of right behind the barrier (A/B switch)
+    // (third generation: 1 = late; role-split kernels: bit 0 no priorities, bit 1 nt stores, bit 2 nt loads)
+    static const int fl = pk_experiment_int("rec_flush_late", 0);
+    a.flush_late = fl;
     return 0;
 }
-int pk_rec2_check_residency(const void* kernel, int threads, size_t lds, int grid, const char* who) {
+static int prepare(R2Args& a, Plan2& pl, Rec2PlanFn plan, bool backward, int cell, int act, int T, int B, int bidir, int H) {
+    const int ndir = 1 + bidir;
+    int rc = plan(B * ndir, H, pl);
+    if (rc) return rc;
+    a = R2Args{};
+    a.T = T; a.B = B; a.R = B * ndir; a.H = H; a.Hp = (H + 7) & ~7; a.YH = ndir * H; a.act = act;
+    a.C = pl.C; a.Pn = pl.Pn; a.rpc = pl.rpc;
+    return pk_rec2_host_setup(a, backward, cell);
+}
+int pk_rec2_prepare_fwd(R2Args& a, Plan2& pl, Rec2PlanFn plan, int cell, int act, int T, int B, int bidir, int H, int64_t pitch,
+                        const float* P, const float* pscale, const float* pshift, const float* U, const float* mask,
+                        float mask_scalar, float* Y, float* S) {
+    const int rc = prepare(a, pl, plan, false, cell, act, T, B, bidir, H);
+    if (rc) return rc;
+    a.P = P; a.pscale = pscale; a.pshift = pshift; a.U = U; a.mask = mask; a.mask_scalar = mask_scalar;
+    a.Y = Y; a.S = S; a.Ypitch = (int)pitch;
+    return 0;
+}
+int pk_rec2_prepare_bwd(R2Args& a, Plan2& pl, Rec2PlanFn plan, int cell, int act, int T, int B, int bidir, int H, int64_t pitch,
+                        const float* U, const float* mask, float mask_scalar, const float* Y, const float* S, const float* dY,
+                        float* dP2) {
+    const int rc = prepare(a, pl, plan, true, cell, act, T, B, bidir, H);
+    if (rc) return rc;
+    a.U = U; a.mask = mask; a.mask_scalar = mask_scalar;
+    a.Y = const_cast<float*>(Y); a.S = const_cast<float*>(S); a.dY = dY; a.dP2 = dP2; a.Gpitch = (int)pitch;
+    return 0;
+}
+int pk_rec2_f32_self_fill() {
+    static const int v = pk_experiment_digit("rec4_self_fill", 0, 0, 1);
+    return v;
+}
+// The clusters of a persistent launch exchange h_t with each other every step: every workgroup of the grid has to be
+// resident at the same time.  Checks the grid against what the device can hold (occupancy query for this kernel, block
+// size and dynamic LDS x CU count, cached per kernel) - a grid that cannot be co-resident is refused here instead of
+// ending in bounded-spin time-outs.  (Kernels of OTHER streams or processes can still delay a workgroup's start; that
+// only costs time: every spin is bounded at ~10 ms and reported.)
+static int pk_rec2_check_residency(const void* kernel, int threads, size_t lds, int grid, const char* who) {
     struct Entry { const void* k; size_t lds; int threads; int cap; };
     static Entry cache[64];
     static int n_cache = 0;
@@ -872,7 +897,7 @@ int pk_rec2_check_residency(const void* kernel, int threads, size_t lds, int gri
     return 0;
 }
 
-int pk_rec2_reset_handshake(hipStream_t st, R2Args& a) {
+static int pk_rec2_reset_handshake(hipStream_t st, R2Args& a) {
     // generations 1 .. 2^28 - 17 (the table starts out as 0xFF bytes: generation 2^28 - 1, never handed out).  Inside a
     // stream capture the number is baked into the graph, so every replay would find its own words from the replay
     // before: there the table is reset by a memset node in front of the kernel, as it used to be everywhere.
@@ -894,6 +919,30 @@ int pk_rec2_reset_handshake(hipStream_t st, R2Args& a) {
     if (cs != hipStreamCaptureStatusNone) PK_CHECK_HIP(hipMemsetAsync(g2_xcd_tab, 0xFF, XCD_TAB_BYTES, st));
     a.hs_gen = g;
     return 0;
+}
+
+int pk_rec2_run(hipStream_t st, R2Args& a, const Plan2& pl, int cell, bool backward, Rec2Kernel k, int threads, size_t lds,
+                const char* who, const PkLnHost* ln, Rec2Help help_policy) {
+    int rc = pk_rec2_ln_setup(st, a, pl, ln, backward);
+    if (rc) return rc;
+    rc = pk_grant_dynamic_lds((const void*)k, lds);  // (exact size: the kernels also hold a little static LDS)
+    if (rc) return rc;
+    const bool proj = help_policy == REC2_HELP_PROJ;
+    for (int l = 0; l < pl.launches; ++l) {
+        a.row0 = l * pl.C * pl.rpc;
+        a.ln_cg0 = l * pl.C;
+        rc = pk_rec2_reset_handshake(st, a);
+        if (rc) return rc;
+        rc = pk_rec2_check_residency((const void*)k, threads, lds, pl.C * pl.Pn, who);
+        if (rc) return rc;
+        const int help = (ln || help_policy == REC2_HELP_NONE) ? 0 : pk_rec_helper_wanted(backward, pl.launches, cell) & (proj ? 1 : 7);
+        if (help && (rc = pk_rec_helper_fork(st)) != 0) return rc;
+        hipLaunchKernelGGL(k, dim3(pl.C * pl.Pn), dim3(threads), lds, st, a);
+        PK_LAUNCH_CHECK();
+        if (help && (rc = pk_rec_helper_launch(st, a, pl, pk_cell_gates(cell), proj ? 0 : pk_cell_saved(cell), backward, !proj, help)) != 0)
+            return rc;
+    }
+    return backward ? pk_rec2_ln_finish(st, a, ln) : 0;
 }
 
 // Does the bf16 persistent kernel of this cell keep its exchange buffer filled by itself (prefilled = 2)?
@@ -919,23 +968,21 @@ extern "C" void pk_persist2_error_reset(void) {
     if (g2_err_host) *g2_err_host = 0u;
 }
 
-typedef void (*Rec2Kernel)(R2Args);
-inline int act_slot(int act) { return act == PK_ACT_RELU ? 0 : act == PK_ACT_TANH ? 1 : 2; }
 // the phase trace (pk_persist2_set_trace, tools/trace_rec2.py) is compiled into the Li-GRU / relu kernels only
 template <int CELL>
 Rec2Kernel pick_fwd(int act) {
-    return act == PK_ACT_RELU ? rec2_fwd_kernel<CELL, PK_ACT_RELU, false>
-         : act == PK_ACT_TANH ? rec2_fwd_kernel<CELL, PK_ACT_TANH, false> : rec2_fwd_kernel<CELL, -1, false>;
+    return pk_rec2_pick_act(act, rec2_fwd_kernel<CELL, PK_ACT_RELU, false>, rec2_fwd_kernel<CELL, PK_ACT_TANH, false>,
+                            rec2_fwd_kernel<CELL, -1, false>);
 }
 template <int CELL>
 Rec2Kernel pick_fwd_nosave(int act) {  // (S == null: validation / forward chunks)
-    return act == PK_ACT_RELU ? rec2_fwd_kernel<CELL, PK_ACT_RELU, false, false, true>
-         : act == PK_ACT_TANH ? rec2_fwd_kernel<CELL, PK_ACT_TANH, false, false, true> : rec2_fwd_kernel<CELL, -1, false, false, true>;
+    return pk_rec2_pick_act(act, rec2_fwd_kernel<CELL, PK_ACT_RELU, false, false, true>,
+                            rec2_fwd_kernel<CELL, PK_ACT_TANH, false, false, true>, rec2_fwd_kernel<CELL, -1, false, false, true>);
 }
 template <int CELL>
 Rec2Kernel pick_bwd(int act) {
-    return act == PK_ACT_RELU ? rec2_bwd_kernel<CELL, PK_ACT_RELU, false>
-         : act == PK_ACT_TANH ? rec2_bwd_kernel<CELL, PK_ACT_TANH, false> : rec2_bwd_kernel<CELL, -1, false>;
+    return pk_rec2_pick_act(act, rec2_bwd_kernel<CELL, PK_ACT_RELU, false>, rec2_bwd_kernel<CELL, PK_ACT_TANH, false>,
+                            rec2_bwd_kernel<CELL, -1, false>);
 }
 inline bool traced(int cell, int act) { return g2_trace != nullptr && cell == PK_CELL_LIGRU && act == PK_ACT_RELU; }
 // (the LayerNorm variants exist with the run-time activation only: no shipped recipe normalises h_t)
@@ -960,69 +1007,44 @@ static int rec_fwd_bf16_impl(void* stream, int cell, int act, int T, int B, int 
                              const float* pscale, const float* pshift, const float* U, const float* mask,
                              float mask_scalar, float* Y, float* S, uint16_t* Yb, int64_t y_pitch, int prefilled,
                              const PkLnHost* ln) {
-    int rc = pk_rec2_check("pk_rec_fwd_bf16", 1, cell, T, B, bidir, H);
+    const char* who = "pk_rec_fwd_bf16";
+    int rc = pk_rec2_check(who, 1, cell, T, B, bidir, H);
     if (rc) return rc;
     // S == null: a validation / forward chunk, nothing is saved for a backward pass; Y == null with it: an inner layer of a
     // stack, whose output is the bf16 copy Yb alone
     PK_REQUIRE(S != nullptr || (ln == nullptr && !traced(cell, act)), "pk_rec_fwd_bf16: S may be null only without per-step LayerNorm");
     PK_REQUIRE(Y != nullptr || S == nullptr, "pk_rec_fwd_bf16: Y may be null only together with S");
     hipStream_t st = pk_stream(stream);
-    const int ndir = 1 + bidir, R = B * ndir, Hp = (H + 7) & ~7;
+    const int ndir = 1 + bidir, Hp = (H + 7) & ~7;
     PK_REQUIRE(y_pitch >= (int64_t)ndir * Hp && (y_pitch % 8) == 0 && ((uintptr_t)Yb & 15) == 0,
                "pk_rec_fwd_bf16: Yb pitch must be a multiple of 8 and hold %d x %d elements", ndir, Hp);
     PK_REQUIRE((double)T * B * y_pitch * 2.0 < 4.0e9, "pk_rec_fwd_bf16: exchange buffer exceeds the 4 GB buffer-descriptor range");
+    R2Args a{};
     Plan2 pl;
-    rc = pk_rec2_make_plan(R, H, pl);
+    rc = pk_rec2_prepare_fwd(a, pl, pk_rec2_make_plan, cell, act, T, B, bidir, H, y_pitch, P, pscale, pshift, U, mask, mask_scalar, Y, S);
     if (rc) return rc;
-    R2Args a;
-    a.T = T; a.B = B; a.R = R; a.H = H; a.Hp = Hp; a.YH = ndir * H; a.act = act;
-    a.C = pl.C; a.Pn = pl.Pn; a.rpc = pl.rpc; a.row0 = 0;
-    a.P = P; a.pscale = pscale; a.pshift = pshift; a.U = U; a.mask = mask; a.mask_scalar = mask_scalar;
-    a.Y = Y; a.S = S; a.Yb = (unsigned short*)Yb; a.Xb = nullptr; a.Ypitch = (int)y_pitch;
-    a.dY = nullptr; a.dP2 = nullptr; a.dGb = nullptr; a.Gpitch = 0;
-    rc = pk_rec2_host_setup(a, false, cell);
-    if (rc) return rc;
+    a.Yb = (unsigned short*)Yb;
     // the bf16 layer output is the mailbox: it must hold the sentinel wherever a poll can arrive before its data.
     // prefilled: 1 = the caller filled it, 2 = fill it on the way if this kernel can (pk_rec_self_fill), 0 = fill here
-    const bool lstm8 = cell == PK_CELL_LSTM && pk_rec2l_enabled();
     a.self_fill = prefilled == 2 ? 1 : 0;
     if (prefilled != 1 && !a.self_fill) PK_CHECK_HIP(hipMemsetAsync(Yb, 0xFF, (size_t)T * B * y_pitch * 2, st));
-    rc = pk_rec2_ln_setup(st, a, pl, ln, false);
-    if (rc) return rc;
     // (per-step LayerNorm lives in the four-wave second-generation kernels of this file, for every cell)
-    if (lstm8 && !ln) return pk_rec2l_launch(st, a, pl, act, false);
-    if (!ln && pk_rec3_covers(cell, 0)) return pk_rec3_launch(st, a, pl, cell, act, false, traced(cell, act));
-    const int G = pk_cell_gates(cell);
-    const size_t lds = 2 * (size_t)RMAX * pk_r2_lda_bf16(KPAD) * 2 + 4 * ((size_t)(G + 1 + pk_cell_saved(cell) + (ln ? 1 : 0)) * 1024 + 512) + 16;
+    size_t lds;
+    if (!ln && cell == PK_CELL_LSTM && pk_rec2l_enabled()) {
+        const Rec2Kernel k8 = pk_rec2l_kernel(a, act, false, &lds);
+        return pk_rec2_run(st, a, pl, cell, false, k8, 512, lds, "pk_rec_*_bf16 (LSTM, eight waves)", ln, REC2_HELP_FULL);
+    }
+    if (!ln && pk_rec3_covers(cell, 0)) {
+        const Rec2Kernel k3 = pk_rec3_kernel(cell, act, false, traced(cell, act), &lds);
+        return pk_rec2_run(st, a, pl, cell, false, k3, 256, lds, who, ln, REC2_HELP_FULL);
+    }
+    lds = 2 * (size_t)RMAX * pk_r2_lda_bf16(KPAD) * 2 + 4 * ((size_t)(pk_cell_gates(cell) + 1 + pk_cell_saved(cell) + (ln ? 1 : 0)) * 1024 + 512) + 16;
     const bool nosave = S == nullptr;
     const Rec2Kernel k = ln ? pick_fwd_ln(cell)
                        : nosave ? (cell == PK_CELL_LIGRU ? pick_fwd_nosave<PK_CELL_LIGRU>(act) : cell == PK_CELL_RNN ? pick_fwd_nosave<PK_CELL_RNN>(act)
                                                                                                                       : pick_fwd_nosave<PK_CELL_LSTM>(act))
                                 : pick_fwd(cell, act);
-    {   // dynamic LDS above the 64 KB default needs the opt-in (exact size: the kernels also hold a little static LDS)
-        static size_t granted[3][8] = {{0}, {0}, {0}};  // hipFuncSetAttribute is slow (milliseconds): once per kernel and size
-        const int slot = cell == PK_CELL_LIGRU ? 0 : cell == PK_CELL_RNN ? 1 : 2;
-        const int as = ln ? 4 : nosave ? 5 + act_slot(act) : traced(cell, act) ? 3 : act_slot(act);
-        if (granted[slot][as] < lds) {
-            PK_CHECK_HIP(hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            granted[slot][as] = lds;
-        }
-    }
-    for (int l = 0; l < pl.launches; ++l) {
-        a.row0 = l * pl.C * pl.rpc;
-        a.ln_cg0 = l * pl.C;
-        rc = pk_rec2_reset_handshake(st, a);
-        if (rc) return rc;
-        dim3 grid(pl.C * pl.Pn), block(256);
-        rc = pk_rec2_check_residency((const void*)k, 256, lds, pl.C * pl.Pn, "pk_rec_fwd_bf16");
-        if (rc) return rc;
-        const int help = ln ? 0 : pk_rec_helper_wanted(false, pl.launches, cell);
-        if (help && (rc = pk_rec_helper_fork(st)) != 0) return rc;
-        hipLaunchKernelGGL(k, grid, block, lds, st, a);
-        PK_LAUNCH_CHECK();
-        if (help && (rc = pk_rec_helper_launch(st, a, pl, G, pk_cell_saved(cell), false, true, help)) != 0) return rc;
-    }
-    return 0;
+    return pk_rec2_run(st, a, pl, cell, false, k, 256, lds, who, ln, REC2_HELP_FULL);
 }
 extern "C" int pk_rec_fwd_bf16(void* stream, int cell, int act, int T, int B, int bidir, int H, const float* P,
                                const float* pscale, const float* pshift, const float* U, const float* mask,
@@ -1045,59 +1067,34 @@ extern "C" int pk_rec_fwd_bf16_ln(void* stream, int cell, int act, int T, int B,
 static int rec_bwd_bf16_impl(void* stream, int cell, int act, int T, int B, int bidir, int H, const float* U,
                              const float* mask, float mask_scalar, const float* Y, const float* S, const float* dY,
                              float* dP2, uint16_t* dGb, int64_t g_pitch, int prefilled, const PkLnHost* ln) {
-    int rc = pk_rec2_check("pk_rec_bwd_bf16", 1, cell, T, B, bidir, H);
+    const char* who = "pk_rec_bwd_bf16";
+    int rc = pk_rec2_check(who, 1, cell, T, B, bidir, H);
     if (rc) return rc;
     hipStream_t st = pk_stream(stream);
-    const int ndir = 1 + bidir, R = B * ndir, Hp = (H + 7) & ~7, G = pk_cell_gates(cell);
+    const int ndir = 1 + bidir, Hp = (H + 7) & ~7, G = pk_cell_gates(cell);
     PK_REQUIRE(g_pitch >= (int64_t)G * Hp && (g_pitch % 8) == 0 && ((uintptr_t)dGb & 15) == 0,
                "pk_rec_bwd_bf16: dGb pitch must be a multiple of 8 and hold %d x %d elements", G, Hp);
     PK_REQUIRE((double)ndir * T * B * g_pitch * 2.0 < 4.0e9, "pk_rec_bwd_bf16: exchange buffer exceeds the 4 GB buffer-descriptor range");
+    R2Args a{};
     Plan2 pl;
-    rc = pk_rec2_make_plan(R, H, pl);
+    rc = pk_rec2_prepare_bwd(a, pl, pk_rec2_make_plan, cell, act, T, B, bidir, H, g_pitch, U, mask, mask_scalar, Y, S, dY, dP2);
     if (rc) return rc;
-    R2Args a;
-    a.T = T; a.B = B; a.R = R; a.H = H; a.Hp = Hp; a.YH = ndir * H; a.act = act;
-    a.C = pl.C; a.Pn = pl.Pn; a.rpc = pl.rpc; a.row0 = 0;
-    a.P = nullptr; a.pscale = nullptr; a.pshift = nullptr; a.U = U; a.mask = mask; a.mask_scalar = mask_scalar;
-    a.Y = const_cast<float*>(Y); a.S = const_cast<float*>(S); a.Yb = nullptr; a.Xb = nullptr; a.Ypitch = 0;
-    a.dY = dY; a.dP2 = dP2; a.dGb = (unsigned short*)dGb; a.Gpitch = (int)g_pitch;
-    rc = pk_rec2_host_setup(a, true, cell);
-    if (rc) return rc;
-    const bool lstm8 = cell == PK_CELL_LSTM && pk_rec2l_enabled();
+    a.dGb = (unsigned short*)dGb;
     a.self_fill = prefilled == 2 ? 1 : 0;
     if (prefilled != 1 && !a.self_fill) PK_CHECK_HIP(hipMemsetAsync(dGb, 0xFF, (size_t)ndir * T * B * g_pitch * 2, st));
-    rc = pk_rec2_ln_setup(st, a, pl, ln, true);
-    if (rc) return rc;
-    if (lstm8 && !ln) return pk_rec2l_launch(st, a, pl, act, true);
-    if (!ln && pk_rec3_covers(cell, 1)) return pk_rec3_launch(st, a, pl, cell, act, true, traced(cell, act));
+    size_t lds;
+    if (!ln && cell == PK_CELL_LSTM && pk_rec2l_enabled()) {
+        const Rec2Kernel k8 = pk_rec2l_kernel(a, act, true, &lds);
+        return pk_rec2_run(st, a, pl, cell, true, k8, 512, lds, "pk_rec_*_bf16 (LSTM, eight waves)", ln, REC2_HELP_FULL);
+    }
+    if (!ln && pk_rec3_covers(cell, 1)) {
+        const Rec2Kernel k3 = pk_rec3_kernel(cell, act, true, traced(cell, act), &lds);
+        return pk_rec2_run(st, a, pl, cell, true, k3, 256, lds, who, ln, REC2_HELP_FULL);
+    }
     const size_t atile = (size_t)RMAX * pk_r2_lda_bf16(G * KPAD) * 2;
     const int nin = pk_cell_saved(cell) + 2 + (cell == PK_CELL_LSTM ? 1 : 0) + (ln ? 1 : 0);
-    const size_t lds = (2 * atile > 96 * 1024 ? 1 : 2) * atile + 4 * ((size_t)(nin + G) * 1024 + (size_t)G * 512) + 16;
-    const Rec2Kernel k = ln ? pick_bwd_ln(cell) : pick_bwd(cell, act);
-    {
-        static size_t granted[3][5] = {{0, 0, 0, 0, 0}, {0, 0, 0, 0, 0}, {0, 0, 0, 0, 0}};  // hipFuncSetAttribute is slow (milliseconds): once per kernel and size
-        const int slot = cell == PK_CELL_LIGRU ? 0 : cell == PK_CELL_RNN ? 1 : 2;
-        const int as = ln ? 4 : traced(cell, act) ? 3 : act_slot(act);
-        if (granted[slot][as] < lds) {
-            PK_CHECK_HIP(hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            granted[slot][as] = lds;
-        }
-    }
-    for (int l = 0; l < pl.launches; ++l) {
-        a.row0 = l * pl.C * pl.rpc;
-        a.ln_cg0 = l * pl.C;
-        rc = pk_rec2_reset_handshake(st, a);
-        if (rc) return rc;
-        dim3 grid(pl.C * pl.Pn), block(256);
-        rc = pk_rec2_check_residency((const void*)k, 256, lds, pl.C * pl.Pn, "pk_rec_bwd_bf16");
-        if (rc) return rc;
-        const int help = ln ? 0 : pk_rec_helper_wanted(true, pl.launches, cell);
-        if (help && (rc = pk_rec_helper_fork(st)) != 0) return rc;
-        hipLaunchKernelGGL(k, grid, block, lds, st, a);
-        PK_LAUNCH_CHECK();
-        if (help && (rc = pk_rec_helper_launch(st, a, pl, G, pk_cell_saved(cell), true, true, help)) != 0) return rc;
-    }
-    return pk_rec2_ln_finish(st, a, ln);
+    lds = (2 * atile > 96 * 1024 ? 1 : 2) * atile + 4 * ((size_t)(nin + G) * 1024 + (size_t)G * 512) + 16;
+    return pk_rec2_run(st, a, pl, cell, true, ln ? pick_bwd_ln(cell) : pick_bwd(cell, act), 256, lds, who, ln, REC2_HELP_FULL);
 }
 extern "C" int pk_rec_bwd_bf16(void* stream, int cell, int act, int T, int B, int bidir, int H, const float* U,
                                const float* mask, float mask_scalar, const float* Y, const float* S, const float* dY,

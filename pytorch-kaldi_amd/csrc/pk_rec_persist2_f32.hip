@@ -611,39 +611,18 @@ __global__ __launch_bounds__(256, 1) void rec2f_bwd_kernel(R2Args a) {
     }
 }
 
-typedef void (*Rec2fKernel)(R2Args);
 // (the LayerNorm variants exist with the run-time activation only: no shipped recipe normalises h_t)
 template <int CELL>
-Rec2fKernel pickf_fwd(int act, bool ln) {
+Rec2Kernel pickf_fwd(int act, bool ln) {
     if (ln) return rec2f_fwd_kernel<CELL, -1, true>;
-    return act == PK_ACT_RELU ? rec2f_fwd_kernel<CELL, PK_ACT_RELU, false>
-         : act == PK_ACT_TANH ? rec2f_fwd_kernel<CELL, PK_ACT_TANH, false> : rec2f_fwd_kernel<CELL, -1, false>;
+    return pk_rec2_pick_act(act, rec2f_fwd_kernel<CELL, PK_ACT_RELU, false>, rec2f_fwd_kernel<CELL, PK_ACT_TANH, false>,
+                            rec2f_fwd_kernel<CELL, -1, false>);
 }
 template <int CELL>
-Rec2fKernel pickf_bwd(int act, bool ln) {
+Rec2Kernel pickf_bwd(int act, bool ln) {
     if (ln) return rec2f_bwd_kernel<CELL, -1, true>;
-    return act == PK_ACT_RELU ? rec2f_bwd_kernel<CELL, PK_ACT_RELU, false>
-         : act == PK_ACT_TANH ? rec2f_bwd_kernel<CELL, PK_ACT_TANH, false> : rec2f_bwd_kernel<CELL, -1, false>;
-}
-
-int self_fill2f() {
-    static int v = -1;
-    if (v < 0) {
-        const char* e = pk_experiment("rec4_self_fill");
-        v = (e && e[0] == '0') ? 0 : 1;
-    }
-    return v;
-}
-
-int grant_lds(Rec2fKernel k, size_t lds) {
-    struct Entry { Rec2fKernel k; size_t lds; };
-    static Entry granted[16];
-    static int n = 0;
-    for (int i = 0; i < n; ++i)
-        if (granted[i].k == k && granted[i].lds >= lds) return 0;
-    PK_CHECK_HIP(hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    if (n < 16) granted[n++] = Entry{k, lds};
-    return 0;
+    return pk_rec2_pick_act(act, rec2f_bwd_kernel<CELL, PK_ACT_RELU, false>, rec2f_bwd_kernel<CELL, PK_ACT_TANH, false>,
+                            rec2f_bwd_kernel<CELL, -1, false>);
 }
 
 }  // namespace
@@ -664,86 +643,46 @@ int64_t pk_rec2f_exchange_floats(int cell, int T, int B, int bidir, int H) {
 int pk_rec2f_fwd(hipStream_t st, int cell, int act, int T, int B, int bidir, int H, const float* P, const float* pscale,
                  const float* pshift, const float* U, const float* mask, float mask_scalar, float* Y, float* S, float* Yx,
                  const PkLnHost* ln) {
-    int rc = pk_rec2_check("pk_rec_fwd (fp32, persistent)", pk_rec2f_covers(cell, H), cell, T, B, bidir, H);
+    const char* who = "pk_rec_fwd (fp32, persistent)";
+    int rc = pk_rec2_check(who, pk_rec2f_covers(cell, H), cell, T, B, bidir, H);
     if (rc) return rc;
-    const int ndir = 1 + bidir, R = B * ndir, Hp = (H + 7) & ~7;
+    const int ndir = 1 + bidir, Hp = (H + 7) & ~7;
     const int64_t y_pitch = ((int64_t)ndir * Hp + 15) / 16 * 16;
     PK_REQUIRE(((uintptr_t)Yx & 15) == 0, "pk_rec_fwd: exchange buffer must be 16-byte aligned");
     PK_REQUIRE((double)T * B * y_pitch * 4.0 < 4.0e9, "pk_rec_fwd (fp32, persistent): exchange buffer exceeds the 4 GB buffer-descriptor range");
+    R2Args a{};
     Plan2 pl;
-    rc = pk_rec2_make_plan(R, H, pl);
+    rc = pk_rec2_prepare_fwd(a, pl, pk_rec2_make_plan, cell, act, T, B, bidir, H, y_pitch, P, pscale, pshift, U, mask, mask_scalar, Y, S);
     if (rc) return rc;
-    R2Args a;
-    a.T = T; a.B = B; a.R = R; a.H = H; a.Hp = Hp; a.YH = ndir * H; a.act = act;
-    a.C = pl.C; a.Pn = pl.Pn; a.rpc = pl.rpc; a.row0 = 0;
-    a.P = P; a.pscale = pscale; a.pshift = pshift; a.U = U; a.mask = mask; a.mask_scalar = mask_scalar;
-    a.Y = Y; a.S = S; a.Yb = nullptr; a.Xb = nullptr; a.Ypitch = (int)y_pitch;
-    a.dY = nullptr; a.dP2 = nullptr; a.dGb = nullptr; a.Gpitch = 0;
-    a.Yx = Yx; a.dGx = nullptr;
-    rc = pk_rec2_host_setup(a, false, cell);
-    if (rc) return rc;
-    a.self_fill = self_fill2f();
+    a.Yx = Yx;
+    a.self_fill = pk_rec2_f32_self_fill();
     // the mailbox: every dword "not written yet" - written by the kernel itself a few steps ahead of its publishes, or
     // (PK_EXPERIMENT rec4_self_fill=0, one switch for both fp32 generations) by one fill in front of the launches
     if (!a.self_fill) PK_CHECK_HIP(hipMemsetAsync(Yx, 0xFF, (size_t)T * B * y_pitch * 4, st));
-    rc = pk_rec2_ln_setup(st, a, pl, ln, false);
-    if (rc) return rc;
     const int G = pk_cell_gates(cell);
     const size_t lds = 2 * (size_t)RMAX * pk_r2_lda_f32(KPAD) * 4 + 4 * ((size_t)(G + 1 + pk_cell_saved(cell) + (ln ? 1 : 0)) * 1024) + 16;
-    const Rec2fKernel k = cell == PK_CELL_LIGRU ? pickf_fwd<PK_CELL_LIGRU>(act, ln != nullptr) : pickf_fwd<PK_CELL_RNN>(act, ln != nullptr);
-    rc = grant_lds(k, lds);
-    if (rc) return rc;
-    for (int l = 0; l < pl.launches; ++l) {
-        a.row0 = l * pl.C * pl.rpc;
-        a.ln_cg0 = l * pl.C;
-        rc = pk_rec2_reset_handshake(st, a);
-        if (rc) return rc;
-        rc = pk_rec2_check_residency((const void*)k, 256, lds, pl.C * pl.Pn, "pk_rec_fwd (fp32, persistent)");
-        if (rc) return rc;
-        hipLaunchKernelGGL(k, dim3(pl.C * pl.Pn), dim3(256), lds, st, a);
-        PK_LAUNCH_CHECK();
-    }
-    return 0;
+    const Rec2Kernel k = cell == PK_CELL_LIGRU ? pickf_fwd<PK_CELL_LIGRU>(act, ln != nullptr) : pickf_fwd<PK_CELL_RNN>(act, ln != nullptr);
+    return pk_rec2_run(st, a, pl, cell, false, k, 256, lds, who, ln, REC2_HELP_NONE);
 }
 
 int pk_rec2f_bwd(hipStream_t st, int cell, int act, int T, int B, int bidir, int H, const float* U, const float* mask,
                  float mask_scalar, const float* Y, const float* S, const float* dY, float* dP2, float* dGx, const PkLnHost* ln) {
-    int rc = pk_rec2_check("pk_rec_bwd (fp32, persistent)", pk_rec2f_covers(cell, H), cell, T, B, bidir, H);
+    const char* who = "pk_rec_bwd (fp32, persistent)";
+    int rc = pk_rec2_check(who, pk_rec2f_covers(cell, H), cell, T, B, bidir, H);
     if (rc) return rc;
-    const int ndir = 1 + bidir, R = B * ndir, Hp = (H + 7) & ~7, G = pk_cell_gates(cell);
+    const int ndir = 1 + bidir, Hp = (H + 7) & ~7, G = pk_cell_gates(cell);
     const int64_t g_pitch = ((int64_t)G * Hp + 15) / 16 * 16;
     PK_REQUIRE(((uintptr_t)dGx & 15) == 0, "pk_rec_bwd: exchange buffer must be 16-byte aligned");
     PK_REQUIRE((double)ndir * T * B * g_pitch * 4.0 < 4.0e9, "pk_rec_bwd (fp32, persistent): exchange buffer exceeds the 4 GB buffer-descriptor range");
+    R2Args a{};
     Plan2 pl;
-    rc = pk_rec2_make_plan(R, H, pl);
+    rc = pk_rec2_prepare_bwd(a, pl, pk_rec2_make_plan, cell, act, T, B, bidir, H, g_pitch, U, mask, mask_scalar, Y, S, dY, dP2);
     if (rc) return rc;
-    R2Args a;
-    a.T = T; a.B = B; a.R = R; a.H = H; a.Hp = Hp; a.YH = ndir * H; a.act = act;
-    a.C = pl.C; a.Pn = pl.Pn; a.rpc = pl.rpc; a.row0 = 0;
-    a.P = nullptr; a.pscale = nullptr; a.pshift = nullptr; a.U = U; a.mask = mask; a.mask_scalar = mask_scalar;
-    a.Y = const_cast<float*>(Y); a.S = const_cast<float*>(S); a.Yb = nullptr; a.Xb = nullptr; a.Ypitch = 0;
-    a.dY = dY; a.dP2 = dP2; a.dGb = nullptr; a.Gpitch = (int)g_pitch;
-    a.Yx = nullptr; a.dGx = dGx;
-    rc = pk_rec2_host_setup(a, true, cell);
-    if (rc) return rc;
-    a.self_fill = self_fill2f();
+    a.dGx = dGx;
+    a.self_fill = pk_rec2_f32_self_fill();
     if (!a.self_fill) PK_CHECK_HIP(hipMemsetAsync(dGx, 0xFF, (size_t)ndir * T * B * g_pitch * 4, st));
-    rc = pk_rec2_ln_setup(st, a, pl, ln, true);
-    if (rc) return rc;
     const size_t atile = (size_t)RMAX * pk_r2_lda_f32(G * KPAD) * 4;
     const size_t lds = (2 * atile > 100 * 1024 ? 1 : 2) * atile + 4 * ((size_t)(pk_cell_saved(cell) + 2 + (ln ? 1 : 0) + G) * 1024) + 16;
-    const Rec2fKernel k = cell == PK_CELL_LIGRU ? pickf_bwd<PK_CELL_LIGRU>(act, ln != nullptr) : pickf_bwd<PK_CELL_RNN>(act, ln != nullptr);
-    rc = grant_lds(k, lds);
-    if (rc) return rc;
-    for (int l = 0; l < pl.launches; ++l) {
-        a.row0 = l * pl.C * pl.rpc;
-        a.ln_cg0 = l * pl.C;
-        rc = pk_rec2_reset_handshake(st, a);
-        if (rc) return rc;
-        rc = pk_rec2_check_residency((const void*)k, 256, lds, pl.C * pl.Pn, "pk_rec_bwd (fp32, persistent)");
-        if (rc) return rc;
-        hipLaunchKernelGGL(k, dim3(pl.C * pl.Pn), dim3(256), lds, st, a);
-        PK_LAUNCH_CHECK();
-    }
-    return pk_rec2_ln_finish(st, a, ln);
+    const Rec2Kernel k = cell == PK_CELL_LIGRU ? pickf_bwd<PK_CELL_LIGRU>(act, ln != nullptr) : pickf_bwd<PK_CELL_RNN>(act, ln != nullptr);
+    return pk_rec2_run(st, a, pl, cell, true, k, 256, lds, who, ln, REC2_HELP_NONE);
 }

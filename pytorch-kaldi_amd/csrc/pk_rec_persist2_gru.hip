@@ -935,39 +935,26 @@ __global__ __launch_bounds__(256, 1) void rec3g_bwd_kernel(R2Args a) {
     }
 }
 
-size_t granted_lds[2][2][3] = {{{0, 0, 0}, {0, 0, 0}}, {{0, 0, 0}, {0, 0, 0}}};
-typedef void (*Rec2gKernel)(R2Args);
-inline int act_slot(int act) { return act == PK_ACT_RELU ? 0 : act == PK_ACT_TANH ? 1 : 2; }
 template <int CELL>
-Rec2gKernel pick_fwd(int act) {
-    return act == PK_ACT_RELU ? rec2g_fwd_kernel<CELL, PK_ACT_RELU> : act == PK_ACT_TANH ? rec2g_fwd_kernel<CELL, PK_ACT_TANH>
-                                                                                        : rec2g_fwd_kernel<CELL, -1>;
+Rec2Kernel pick_fwd(int act) {
+    return pk_rec2_pick_act(act, rec2g_fwd_kernel<CELL, PK_ACT_RELU>, rec2g_fwd_kernel<CELL, PK_ACT_TANH>, rec2g_fwd_kernel<CELL, -1>);
 }
 template <int CELL>
-Rec2gKernel pick_bwd(int act) {
-    return act == PK_ACT_RELU ? rec2g_bwd_kernel<CELL, PK_ACT_RELU> : act == PK_ACT_TANH ? rec2g_bwd_kernel<CELL, PK_ACT_TANH>
-                                                                                        : rec2g_bwd_kernel<CELL, -1>;
+Rec2Kernel pick_bwd(int act) {
+    return pk_rec2_pick_act(act, rec2g_bwd_kernel<CELL, PK_ACT_RELU>, rec2g_bwd_kernel<CELL, PK_ACT_TANH>, rec2g_bwd_kernel<CELL, -1>);
 }
-
 template <int CELL>
-Rec2gKernel pick_bwd3(int act) {
-    return act == PK_ACT_RELU ? rec3g_bwd_kernel<CELL, PK_ACT_RELU> : act == PK_ACT_TANH ? rec3g_bwd_kernel<CELL, PK_ACT_TANH>
-                                                                                        : rec3g_bwd_kernel<CELL, -1>;
+Rec2Kernel pick_bwd3(int act) {
+    return pk_rec2_pick_act(act, rec3g_bwd_kernel<CELL, PK_ACT_RELU>, rec3g_bwd_kernel<CELL, PK_ACT_TANH>, rec3g_bwd_kernel<CELL, -1>);
 }
 // PK_EXPERIMENT gru_bwd_gen=3 selects the third-generation backward kernel.  NOT the default: on the two-phase step it measured
 // slower (libri_gru 35.7 vs 34.7 ms per step, two rounds on one box) - the loads and fill stores issued behind barrier 1
 // sit in front of the vmcnt(0) of the phase-2 poll half a step later, and without the patch traffic in between the fill
 // stores' HBM acknowledge is still outstanding there.  (The one-hop kernels gain: liGRU -12 %, LSTM -5 % of the step.)
 inline bool bwd_gen3() {
-    static int g = -1;
-    if (g < 0) {
-        const char* e = pk_experiment("gru_bwd_gen");
-        g = (e && e[0] == '3') ? 3 : 2;
-    }
+    static const int g = pk_experiment_digit("gru_bwd_gen", 3, 3, 2);
     return g == 3;
 }
-size_t granted_lds3[2][3] = {{0, 0, 0}, {0, 0, 0}};
-size_t granted_ln[2][2] = {{0, 0}, {0, 0}};  // [fwd / bwd][GRU / minimalGRU]: the LayerNorm variants (run-time activation only)
 
 int rec2p_fwd_impl(void* stream, int cell, int act, int T, int B, int bidir, int H, const float* P,
                    const float* pscale, const float* pshift, const float* U, const float* mask,
@@ -976,51 +963,23 @@ int rec2p_fwd_impl(void* stream, int cell, int act, int T, int B, int bidir, int
     int rc = pk_rec2_check("pk_rec2p_fwd_bf16", cell == PK_CELL_GRU || cell == PK_CELL_MINGRU, cell, T, B, bidir, H);
     if (rc) return rc;
     hipStream_t st = pk_stream(stream);
-    const int ndir = 1 + bidir, R = B * ndir, Hp = (H + 7) & ~7, G = pk_cell_gates(cell);
+    const int ndir = 1 + bidir, Hp = (H + 7) & ~7, G = pk_cell_gates(cell);
     PK_REQUIRE(y_pitch >= (int64_t)ndir * Hp && (y_pitch % 8) == 0 && ((uintptr_t)Yb & 15) == 0 && ((uintptr_t)Xb & 15) == 0,
                "pk_rec2p_fwd_bf16: Yb / Xb pitch must be a multiple of 8 and hold %d x %d elements", ndir, Hp);
     PK_REQUIRE((double)T * B * y_pitch * 2.0 < 4.0e9, "pk_rec2p_fwd_bf16: exchange buffer exceeds the 4 GB buffer-descriptor range");
+    R2Args a{};
     Plan2 pl;
-    rc = pk_rec2_make_plan(R, H, pl);
+    rc = pk_rec2_prepare_fwd(a, pl, pk_rec2_make_plan, cell, act, T, B, bidir, H, y_pitch, P, pscale, pshift, U, mask, mask_scalar, Y, S);
     if (rc) return rc;
-    R2Args a;
-    a.T = T; a.B = B; a.R = R; a.H = H; a.Hp = Hp; a.YH = ndir * H; a.act = act;
-    a.C = pl.C; a.Pn = pl.Pn; a.rpc = pl.rpc; a.row0 = 0;
-    a.P = P; a.pscale = pscale; a.pshift = pshift; a.U = U; a.mask = mask; a.mask_scalar = mask_scalar;
-    a.Y = Y; a.S = S; a.Yb = (unsigned short*)Yb; a.Xb = (unsigned short*)Xb; a.Ypitch = (int)y_pitch;
-    a.dY = nullptr; a.dP2 = nullptr; a.dGb = nullptr; a.Gpitch = 0;
-    rc = pk_rec2_host_setup(a, false, cell);
-    if (rc) return rc;
+    a.Yb = (unsigned short*)Yb; a.Xb = (unsigned short*)Xb;
     a.self_fill = prefilled == 2 ? 1 : 0;  // (prefilled: see pk_rec_fwd_bf16)
     if (!prefilled) PK_CHECK_HIP(hipMemsetAsync(Yb, 0xFF, (size_t)T * B * y_pitch * 2, st));
     if (!prefilled) PK_CHECK_HIP(hipMemsetAsync(Xb, 0xFF, (size_t)T * B * y_pitch * 2, st));
-    rc = pk_rec2_ln_setup(st, a, pl, ln, false);
-    if (rc) return rc;
     const size_t lds = 2 * (size_t)RMAX * pk_r2_lda_bf16(KPAD) * 2 + 4 * ((size_t)(2 * G + 1 + (ln ? 1 : 0)) * 1024 + 512) + 16;
-    const int slot = cell == PK_CELL_GRU ? 0 : 1;
-    const Rec2gKernel fn = ln ? (cell == PK_CELL_GRU ? rec2g_fwd_kernel<PK_CELL_GRU, -1, true> : rec2g_fwd_kernel<PK_CELL_MINGRU, -1, true>)
-                              : (cell == PK_CELL_GRU ? pick_fwd<PK_CELL_GRU>(act) : pick_fwd<PK_CELL_MINGRU>(act));
-    size_t& granted = ln ? granted_ln[0][slot] : granted_lds[0][slot][act_slot(act)];
-    if (granted < lds) {
-        PK_CHECK_HIP(hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        granted = lds;
-    }
-    for (int l = 0; l < pl.launches; ++l) {
-        a.row0 = l * pl.C * pl.rpc;
-        a.ln_cg0 = l * pl.C;
-        rc = pk_rec2_reset_handshake(st, a);
-        if (rc) return rc;
-        dim3 grid(pl.C * pl.Pn), block(256);
-        rc = pk_rec2_check_residency((const void*)fn, 256, lds, pl.C * pl.Pn, "pk_rec2p_*_bf16");
-        if (rc) return rc;
-        // (forward: the projections only - this cell's S has its own layout)
-        const int help = ln ? 0 : (pk_rec_helper_wanted(false, pl.launches, cell) & 1);
-        if (help && (rc = pk_rec_helper_fork(st)) != 0) return rc;
-        hipLaunchKernelGGL(fn, grid, block, lds, st, a);
-        PK_LAUNCH_CHECK();
-        if (help && (rc = pk_rec_helper_launch(st, a, pl, G, 0, false, false, help)) != 0) return rc;
-    }
-    return 0;
+    const Rec2Kernel fn = ln ? (cell == PK_CELL_GRU ? rec2g_fwd_kernel<PK_CELL_GRU, -1, true> : rec2g_fwd_kernel<PK_CELL_MINGRU, -1, true>)
+                             : (cell == PK_CELL_GRU ? pick_fwd<PK_CELL_GRU>(act) : pick_fwd<PK_CELL_MINGRU>(act));
+    // (forward: the helpers run ahead on the projections only - this cell's S has its own layout)
+    return pk_rec2_run(st, a, pl, cell, false, fn, 256, lds, "pk_rec2p_*_bf16", ln, REC2_HELP_PROJ);
 }
 
 int rec2p_bwd_impl(void* stream, int cell, int act, int T, int B, int bidir, int H, const float* U,
@@ -1029,49 +988,24 @@ int rec2p_bwd_impl(void* stream, int cell, int act, int T, int B, int bidir, int
     int rc = pk_rec2_check("pk_rec2p_bwd_bf16", cell == PK_CELL_GRU || cell == PK_CELL_MINGRU, cell, T, B, bidir, H);
     if (rc) return rc;
     hipStream_t st = pk_stream(stream);
-    const int ndir = 1 + bidir, R = B * ndir, Hp = (H + 7) & ~7, G = pk_cell_gates(cell), G1 = G - 1;
+    const int ndir = 1 + bidir, Hp = (H + 7) & ~7, G = pk_cell_gates(cell), G1 = G - 1;
     PK_REQUIRE(g_pitch >= (int64_t)G * Hp && (g_pitch % 8) == 0 && ((uintptr_t)dGb & 15) == 0,
                "pk_rec2p_bwd_bf16: dGb pitch must be a multiple of 8 and hold %d x %d elements", G, Hp);
     PK_REQUIRE((double)ndir * T * B * g_pitch * 2.0 < 4.0e9, "pk_rec2p_bwd_bf16: exchange buffer exceeds the 4 GB buffer-descriptor range");
+    R2Args a{};
     Plan2 pl;
-    rc = pk_rec2_make_plan(R, H, pl);
+    rc = pk_rec2_prepare_bwd(a, pl, pk_rec2_make_plan, cell, act, T, B, bidir, H, g_pitch, U, mask, mask_scalar, Y, S, dY, nullptr);
     if (rc) return rc;
-    R2Args a;
-    a.T = T; a.B = B; a.R = R; a.H = H; a.Hp = Hp; a.YH = ndir * H; a.act = act;
-    a.C = pl.C; a.Pn = pl.Pn; a.rpc = pl.rpc; a.row0 = 0;
-    a.P = nullptr; a.pscale = nullptr; a.pshift = nullptr; a.U = U; a.mask = mask; a.mask_scalar = mask_scalar;
-    a.Y = const_cast<float*>(Y); a.S = const_cast<float*>(S); a.Yb = nullptr; a.Xb = nullptr; a.Ypitch = 0;
-    a.dY = dY; a.dP2 = nullptr; a.dGb = (unsigned short*)dGb; a.Gpitch = (int)g_pitch;
-    rc = pk_rec2_host_setup(a, true, cell);
-    if (rc) return rc;
+    a.dGb = (unsigned short*)dGb;
     a.self_fill = prefilled == 2 ? 1 : 0;
     if (!prefilled) PK_CHECK_HIP(hipMemsetAsync(dGb, 0xFF, (size_t)ndir * T * B * g_pitch * 2, st));
-    rc = pk_rec2_ln_setup(st, a, pl, ln, true);
-    if (rc) return rc;
     const bool g3 = bwd_gen3() && !ln;  // (the LayerNorm variant exists in the second-generation kernel)
     const size_t tiles = (size_t)RMAX * pk_r2_lda_bf16(G1 * KPAD) * 2 + (size_t)RMAX * pk_r2_lda_bf16(KPAD) * 2;
     const size_t lds = g3 ? tiles + 32 : tiles + 4 * ((size_t)(G + 2 + (ln ? 1 : 0)) * 1024 + (size_t)G * 512) + 16;
-    const int slot = cell == PK_CELL_GRU ? 0 : 1;
-    const Rec2gKernel fn = ln ? (cell == PK_CELL_GRU ? rec2g_bwd_kernel<PK_CELL_GRU, -1, true> : rec2g_bwd_kernel<PK_CELL_MINGRU, -1, true>)
-                         : g3 ? (cell == PK_CELL_GRU ? pick_bwd3<PK_CELL_GRU>(act) : pick_bwd3<PK_CELL_MINGRU>(act))
-                              : (cell == PK_CELL_GRU ? pick_bwd<PK_CELL_GRU>(act) : pick_bwd<PK_CELL_MINGRU>(act));
-    size_t& granted = ln ? granted_ln[1][slot] : g3 ? granted_lds3[slot][act_slot(act)] : granted_lds[1][slot][act_slot(act)];
-    if (granted < lds) {
-        PK_CHECK_HIP(hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        granted = lds;
-    }
-    for (int l = 0; l < pl.launches; ++l) {
-        a.row0 = l * pl.C * pl.rpc;
-        a.ln_cg0 = l * pl.C;
-        rc = pk_rec2_reset_handshake(st, a);
-        if (rc) return rc;
-        dim3 grid(pl.C * pl.Pn), block(256);
-        rc = pk_rec2_check_residency((const void*)fn, 256, lds, pl.C * pl.Pn, "pk_rec2p_*_bf16");
-        if (rc) return rc;
-        hipLaunchKernelGGL(fn, grid, block, lds, st, a);
-        PK_LAUNCH_CHECK();
-    }
-    return pk_rec2_ln_finish(st, a, ln);
+    const Rec2Kernel fn = ln ? (cell == PK_CELL_GRU ? rec2g_bwd_kernel<PK_CELL_GRU, -1, true> : rec2g_bwd_kernel<PK_CELL_MINGRU, -1, true>)
+                        : g3 ? (cell == PK_CELL_GRU ? pick_bwd3<PK_CELL_GRU>(act) : pick_bwd3<PK_CELL_MINGRU>(act))
+                             : (cell == PK_CELL_GRU ? pick_bwd<PK_CELL_GRU>(act) : pick_bwd<PK_CELL_MINGRU>(act));
+    return pk_rec2_run(st, a, pl, cell, true, fn, 256, lds, "pk_rec2p_*_bf16", ln, REC2_HELP_NONE);
 }
 
 }  // namespace

@@ -914,88 +914,48 @@ __global__ __launch_bounds__(512, 1) void rec3l_bwd_kernel(R2Args a) {
     else run(BoolC<1>());
 }
 
-typedef void (*Rec2Kernel)(R2Args);
 Rec2Kernel pick_fwd(int act) {
-    return act == PK_ACT_RELU ? rec2l_fwd_kernel<PK_ACT_RELU> : act == PK_ACT_TANH ? rec2l_fwd_kernel<PK_ACT_TANH> : rec2l_fwd_kernel<-1>;
+    return pk_rec2_pick_act(act, rec2l_fwd_kernel<PK_ACT_RELU>, rec2l_fwd_kernel<PK_ACT_TANH>, rec2l_fwd_kernel<-1>);
 }
 Rec2Kernel pick_bwd(int act) {
-    return act == PK_ACT_RELU ? rec2l_bwd_kernel<PK_ACT_RELU> : act == PK_ACT_TANH ? rec2l_bwd_kernel<PK_ACT_TANH> : rec2l_bwd_kernel<-1>;
+    return pk_rec2_pick_act(act, rec2l_bwd_kernel<PK_ACT_RELU>, rec2l_bwd_kernel<PK_ACT_TANH>, rec2l_bwd_kernel<-1>);
 }
 Rec2Kernel pick_bwd3(int act) {
-    return act == PK_ACT_RELU ? rec3l_bwd_kernel<PK_ACT_RELU> : act == PK_ACT_TANH ? rec3l_bwd_kernel<PK_ACT_TANH> : rec3l_bwd_kernel<-1>;
+    return pk_rec2_pick_act(act, rec3l_bwd_kernel<PK_ACT_RELU>, rec3l_bwd_kernel<PK_ACT_TANH>, rec3l_bwd_kernel<-1>);
 }
 // PK_EXPERIMENT lstm_bwd_gen=2 keeps the second-generation backward kernel (A/B measurements)
 inline bool bwd_gen3() {
-    static int g = -1;
-    if (g < 0) {
-        const char* e = pk_experiment("lstm_bwd_gen");
-        g = (e && e[0] == '2') ? 2 : 3;
-    }
+    static const int g = pk_experiment_digit("lstm_bwd_gen", 2, 2, 3);
     return g == 3;
 }
-inline int act_slot(int act) { return act == PK_ACT_RELU ? 0 : act == PK_ACT_TANH ? 1 : 2; }
-
-}  // namespace
 
 // Which LSTM kernels pk_rec_{fwd,bwd}_bf16 launch: 8 = the ones in this file (default), 4 = the four-wave kernels of
 // pk_rec_persist2.hip (what every other cell uses).  PK_EXPERIMENT lstm_waves=4 changes the default; pk_persist2_set_lstm_waves
 // overrides it at run time (tests/test_gpu_lstm_waves.py compares the two).
-namespace {
-int g_lstm_waves = 0;  // 0: not decided yet
-}
+int g_lstm_waves = 0;  // 0: the default
+
+}  // namespace
+
 int pk_rec2l_enabled() {
-    if (g_lstm_waves == 0) {
-        const char* v = pk_experiment("lstm_waves");
-        g_lstm_waves = (v && atoi(v) == 4) ? 4 : 8;
-    }
-    return g_lstm_waves == 8;
+    static const int dflt = pk_experiment_int("lstm_waves", 8) == 4 ? 4 : 8;
+    return (g_lstm_waves ? g_lstm_waves : dflt) == 8;
 }
 extern "C" void pk_persist2_set_lstm_waves(int waves) { g_lstm_waves = waves == 8 ? 8 : 4; }
 extern "C" int pk_persist2_get_lstm_waves(void) { return pk_rec2l_enabled() ? 8 : 4; }
-int pk_rec2l_helper_delay() {
-    static int d = -1;
-    if (d < 0) {
-        const char* v = pk_experiment("lstm_helper_delay");
-        d = v ? atoi(v) : 4;
-        if (d < 0) d = 0;
-    }
-    return d;
-}
 
-int pk_rec2l_launch(hipStream_t st, R2Args& a, const Plan2& pl, int act, bool backward) {
-    a.helper_delay = pk_rec2l_helper_delay();
-    size_t lds;
-    if (!backward) {
-        lds = 2 * (size_t)RMAX * pk_r2_lda_bf16(KPAD) * 2 + NWV * ((size_t)(GW + 1 + 3) * 1024 + 512) + 4 * GW * 1024 + 16;
-    } else {
-        lds = (size_t)RMAX * pk_r2_lda_bf16(LG * KPAD) * 2 + 4 * ((size_t)(LNS + 3 + LG) * 1024 + LG * 512) + 4 * 1024 +
-              (size_t)((RMAX * LG * (KPAD / 8) + 511) / 512) * 512 * 4 + 16;
-    }
+// The eight-wave kernel of this pass and its dynamic LDS (512 threads); the launches are those of pk_rec_{fwd,bwd}_bf16.
+Rec2Kernel pk_rec2l_kernel(R2Args& a, int act, bool backward, size_t* lds) {
+    static const int delay = pk_experiment_int("lstm_helper_delay", 4);
+    a.helper_delay = delay < 0 ? 0 : delay;
     const bool g3 = backward && bwd_gen3();
-    if (g3)  // A tile | the pairs' input slots | partial sums | LDS table | trash
-        lds = (size_t)RMAX * pk_r2_lda_bf16(LG * KPAD) * 2 + 4 * (size_t)(LNS + 3) * 1024 + 4 * 1024 +
-              (size_t)((RMAX * LG * (KPAD / 8) + 511) / 512) * 512 * 4 + 32;
-    Rec2Kernel k = backward ? (g3 ? pick_bwd3(act) : pick_bwd(act)) : pick_fwd(act);
-    {
-        static size_t granted[3][3] = {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}};  // hipFuncSetAttribute is slow (milliseconds): once per kernel and size
-        size_t& g = granted[backward ? (g3 ? 2 : 1) : 0][act_slot(act)];
-        if (g < lds) {
-            PK_CHECK_HIP(hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            g = lds;
-        }
+    if (!backward) {
+        *lds = 2 * (size_t)RMAX * pk_r2_lda_bf16(KPAD) * 2 + NWV * ((size_t)(GW + 1 + 3) * 1024 + 512) + 4 * GW * 1024 + 16;
+    } else if (g3) {  // A tile | the pairs' input slots | partial sums | LDS table | trash
+        *lds = (size_t)RMAX * pk_r2_lda_bf16(LG * KPAD) * 2 + 4 * (size_t)(LNS + 3) * 1024 + 4 * 1024 +
+               (size_t)((RMAX * LG * (KPAD / 8) + 511) / 512) * 512 * 4 + 32;
+    } else {
+        *lds = (size_t)RMAX * pk_r2_lda_bf16(LG * KPAD) * 2 + 4 * ((size_t)(LNS + 3 + LG) * 1024 + LG * 512) + 4 * 1024 +
+               (size_t)((RMAX * LG * (KPAD / 8) + 511) / 512) * 512 * 4 + 16;
     }
-    for (int l = 0; l < pl.launches; ++l) {
-        a.row0 = l * pl.C * pl.rpc;
-        int rc = pk_rec2_reset_handshake(st, a);
-        if (rc) return rc;
-        dim3 grid(pl.C * pl.Pn), block(512);
-        rc = pk_rec2_check_residency((const void*)k, 512, lds, pl.C * pl.Pn, "pk_rec_*_bf16 (LSTM, eight waves)");
-        if (rc) return rc;
-        const int help = pk_rec_helper_wanted(backward, pl.launches, PK_CELL_LSTM);
-        if (help && (rc = pk_rec_helper_fork(st)) != 0) return rc;
-        hipLaunchKernelGGL(k, grid, block, lds, st, a);
-        PK_LAUNCH_CHECK();
-        if (help && (rc = pk_rec_helper_launch(st, a, pl, 4, pk_cell_saved(PK_CELL_LSTM), backward, true, help)) != 0) return rc;
-    }
-    return 0;
+    return backward ? (g3 ? pick_bwd3(act) : pick_bwd(act)) : pick_fwd(act);
 }

@@ -651,20 +651,25 @@ __global__ __launch_bounds__(256, 1) void rec3_bwd_kernel(R2Args a) {
     }
 }
 
-typedef void (*Rec3Kernel)(R2Args);
 template <int CELL, bool COAL>
-Rec3Kernel pick3_fwd(int act, bool tr) {
+Rec2Kernel pick3_fwd(int act, bool tr) {
     if (tr) return rec3_fwd_kernel<CELL, PK_ACT_RELU, true, COAL>;
-    return act == PK_ACT_RELU ? rec3_fwd_kernel<CELL, PK_ACT_RELU, false, COAL>
-         : act == PK_ACT_TANH ? rec3_fwd_kernel<CELL, PK_ACT_TANH, false, COAL> : rec3_fwd_kernel<CELL, -1, false, COAL>;
+    return pk_rec2_pick_act(act, rec3_fwd_kernel<CELL, PK_ACT_RELU, false, COAL>, rec3_fwd_kernel<CELL, PK_ACT_TANH, false, COAL>,
+                            rec3_fwd_kernel<CELL, -1, false, COAL>);
 }
 template <int CELL, bool COAL>
-Rec3Kernel pick3_bwd(int act, bool tr) {
+Rec2Kernel pick3_bwd(int act, bool tr) {
     if (tr) return rec3_bwd_kernel<CELL, PK_ACT_RELU, true, COAL>;
-    return act == PK_ACT_RELU ? rec3_bwd_kernel<CELL, PK_ACT_RELU, false, COAL>
-         : act == PK_ACT_TANH ? rec3_bwd_kernel<CELL, PK_ACT_TANH, false, COAL> : rec3_bwd_kernel<CELL, -1, false, COAL>;
+    return pk_rec2_pick_act(act, rec3_bwd_kernel<CELL, PK_ACT_RELU, false, COAL>, rec3_bwd_kernel<CELL, PK_ACT_TANH, false, COAL>,
+                            rec3_bwd_kernel<CELL, -1, false, COAL>);
 }
-int g3_gen[2] = {-1, -1};  // per pass (forward, backward): 2 = second generation; 3 = third, HBM accesses through transposer patches; 4 = third, direct
+// per pass (forward, backward): 2 = second generation; 3 = third, HBM accesses through transposer patches; 4 = third, direct
+int gen3(bool backward) {
+    static const int both = pk_experiment_digit("rec_gen", 2, 4, 0);
+    static const int gen[2] = {pk_experiment_digit("rec_gen_fwd", 2, 4, both ? both : 2),
+                               pk_experiment_digit("rec_gen_bwd", 2, 4, both ? both : 4)};
+    return gen[backward ? 1 : 0];
+}
 
 }  // namespace
 
@@ -678,54 +683,21 @@ int g3_gen[2] = {-1, -1};  // per pass (forward, backward): 2 = second generatio
 // so forward stays on the second generation.  PK_EXPERIMENT rec_gen=2 / 3 / 4 forces one generation for both passes,
 // PK_EXPERIMENT rec_gen_fwd / PK_EXPERIMENT rec_gen_bwd for one pass (A/B measurements).
 int pk_rec3_covers(int cell, int backward) {
-    if (g3_gen[0] < 0) {
-        const char* both = pk_experiment("rec_gen");
-        const char* ef = pk_experiment("rec_gen_fwd");
-        const char* eb = pk_experiment("rec_gen_bwd");
-        auto parse = [](const char* e, int dflt) { return (e && e[0] >= '2' && e[0] <= '4') ? e[0] - '0' : dflt; };
-        g3_gen[0] = parse(ef, parse(both, 2));
-        g3_gen[1] = parse(eb, parse(both, 4));
-    }
-    return g3_gen[backward ? 1 : 0] != 2 && (cell == PK_CELL_LIGRU || cell == PK_CELL_RNN);
+    return gen3(backward != 0) != 2 && (cell == PK_CELL_LIGRU || cell == PK_CELL_RNN);
 }
 
-// Launch loop of the third-generation kernels; `a` and `pl` are prepared by pk_rec_fwd_bf16 / pk_rec_bwd_bf16
-// (pk_rec_persist2.hip).  traced: the phase-trace instantiation (Li-GRU / relu only).
-int pk_rec3_launch(hipStream_t st, R2Args& a, const Plan2& pl, int cell, int act, bool backward, bool traced) {
+// The third-generation kernel of this pass and its dynamic LDS; the arguments and the launches are those of
+// pk_rec_fwd_bf16 / pk_rec_bwd_bf16 (pk_rec_persist2.hip).  traced: the phase-trace instantiation (Li-GRU / relu only).
+Rec2Kernel pk_rec3_kernel(int cell, int act, bool backward, bool traced, size_t* lds) {
     const int G = pk_cell_gates(cell), NS = pk_cell_saved(cell);
-    const bool coal = g3_gen[backward ? 1 : 0] != 4;
+    const bool coal = gen3(backward) != 4;
     const size_t atile = (size_t)RMAX * pk_r2_lda_bf16(backward ? G * KPAD : KPAD) * 2;
     const int npatch = backward ? NS + 2 + G : G + 1 + NS;
-    const size_t lds = 2 * atile + 32 + (coal ? (size_t)4 * npatch * PK3_PATCH_F * 4 : 0);
-    Rec3Kernel k;
+    *lds = 2 * atile + 32 + (coal ? (size_t)4 * npatch * PK3_PATCH_F * 4 : 0);
     if (cell == PK_CELL_LIGRU) {
-        if (coal) k = backward ? pick3_bwd<PK_CELL_LIGRU, true>(act, traced) : pick3_fwd<PK_CELL_LIGRU, true>(act, traced);
-        else k = backward ? pick3_bwd<PK_CELL_LIGRU, false>(act, traced) : pick3_fwd<PK_CELL_LIGRU, false>(act, traced);
-    } else {
-        if (coal) k = backward ? pick3_bwd<PK_CELL_RNN, true>(act, false) : pick3_fwd<PK_CELL_RNN, true>(act, false);
-        else k = backward ? pick3_bwd<PK_CELL_RNN, false>(act, false) : pick3_fwd<PK_CELL_RNN, false>(act, false);
+        if (coal) return backward ? pick3_bwd<PK_CELL_LIGRU, true>(act, traced) : pick3_fwd<PK_CELL_LIGRU, true>(act, traced);
+        return backward ? pick3_bwd<PK_CELL_LIGRU, false>(act, traced) : pick3_fwd<PK_CELL_LIGRU, false>(act, traced);
     }
-    {   // dynamic LDS above the 64 KB default needs the opt-in; hipFuncSetAttribute is slow: once per kernel
-        static const void* granted[64];
-        static int n_granted = 0;
-        bool have = false;
-        for (int i = 0; i < n_granted; ++i) have = have || granted[i] == (const void*)k;
-        if (!have) {
-            PK_CHECK_HIP(hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            if (n_granted < 64) granted[n_granted++] = (const void*)k;
-        }
-    }
-    for (int l = 0; l < pl.launches; ++l) {
-        a.row0 = l * pl.C * pl.rpc;
-        int rc = pk_rec2_reset_handshake(st, a);
-        if (rc) return rc;
-        rc = pk_rec2_check_residency((const void*)k, 256, lds, pl.C * pl.Pn, backward ? "pk_rec_bwd_bf16" : "pk_rec_fwd_bf16");
-        if (rc) return rc;
-        const int help = pk_rec_helper_wanted(backward, pl.launches, cell);
-        if (help && (rc = pk_rec_helper_fork(st)) != 0) return rc;
-        hipLaunchKernelGGL(k, dim3(pl.C * pl.Pn), dim3(256), lds, st, a);
-        PK_LAUNCH_CHECK();
-        if (help && (rc = pk_rec_helper_launch(st, a, pl, G, NS, backward, true, help)) != 0) return rc;
-    }
-    return 0;
+    if (coal) return backward ? pick3_bwd<PK_CELL_RNN, true>(act, false) : pick3_fwd<PK_CELL_RNN, true>(act, false);
+    return backward ? pick3_bwd<PK_CELL_RNN, false>(act, false) : pick3_fwd<PK_CELL_RNN, false>(act, false);
 }

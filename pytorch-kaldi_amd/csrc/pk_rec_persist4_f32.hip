@@ -1031,23 +1031,20 @@ __global__ __launch_bounds__(256, 1) void rec4_bwd_kernel(R2Args a) {
     }
 }
 
-typedef void (*Rec4Kernel)(R2Args);
 template <int CELL>
-Rec4Kernel pick4_fwd(int act) {
-    return act == PK_ACT_TANH ? rec4_fwd_kernel<CELL, PK_ACT_TANH> : act == PK_ACT_RELU ? rec4_fwd_kernel<CELL, PK_ACT_RELU>
-                                                                                       : rec4_fwd_kernel<CELL, -1>;
+Rec2Kernel pick4_fwd(int act) {
+    return pk_rec2_pick_act(act, rec4_fwd_kernel<CELL, PK_ACT_RELU>, rec4_fwd_kernel<CELL, PK_ACT_TANH>, rec4_fwd_kernel<CELL, -1>);
 }
 template <int CELL>
-Rec4Kernel pick4_bwd(int act) {
-    return act == PK_ACT_TANH ? rec4_bwd_kernel<CELL, PK_ACT_TANH> : act == PK_ACT_RELU ? rec4_bwd_kernel<CELL, PK_ACT_RELU>
-                                                                                       : rec4_bwd_kernel<CELL, -1>;
+Rec2Kernel pick4_bwd(int act) {
+    return pk_rec2_pick_act(act, rec4_bwd_kernel<CELL, PK_ACT_RELU>, rec4_bwd_kernel<CELL, PK_ACT_TANH>, rec4_bwd_kernel<CELL, -1>);
 }
 // (the LayerNorm variants exist with the run-time activation only: no shipped recipe normalises h_t)
 template <int CELL>
-Rec4Kernel pick4_ln(bool backward) {
-    return backward ? (Rec4Kernel)rec4_bwd_kernel<CELL, -1, true> : (Rec4Kernel)rec4_fwd_kernel<CELL, -1, true>;
+Rec2Kernel pick4_ln(bool backward) {
+    return backward ? (Rec2Kernel)rec4_bwd_kernel<CELL, -1, true> : (Rec2Kernel)rec4_fwd_kernel<CELL, -1, true>;
 }
-Rec4Kernel pick4(int cell, int act, bool backward, bool ln) {
+Rec2Kernel pick4(int cell, int act, bool backward, bool ln) {
     if (ln) {
         switch (cell) {
             case PK_CELL_LSTM: return pick4_ln<PK_CELL_LSTM>(backward);
@@ -1072,26 +1069,6 @@ size_t lds4(int cell, bool backward, bool ln) {
     return ((size_t)2 * (4 * 2 * 256 + (two ? 4 * 2 * 256 : 0)) + 4 * (size_t)(NS + 2 + (ln ? 1 : 0) + G) * 256) * 4;
 }
 
-int grant_lds4(Rec4Kernel k, size_t lds) {
-    struct Entry { Rec4Kernel k; size_t lds; };
-    static Entry granted[32];
-    static int n = 0;
-    for (int i = 0; i < n; ++i)
-        if (granted[i].k == k && granted[i].lds >= lds) return 0;
-    PK_CHECK_HIP(hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    if (n < 32) granted[n++] = Entry{k, lds};
-    return 0;
-}
-
-int self_fill4() {
-    static int v = -1;
-    if (v < 0) {
-        const char* e = pk_experiment("rec4_self_fill");
-        v = (e && e[0] == '0') ? 0 : 1;
-    }
-    return v;
-}
-
 // 32 units per workgroup; as many 16-row clusters per launch as fit the device, a multiple of 8 when there are 8 or more
 // (members of one cluster congruent mod 8: one XCD under round-robin dispatch - speed only)
 int make_plan4(int R, int H, Plan2& pl) {
@@ -1112,12 +1089,9 @@ int make_plan4(int R, int H, Plan2& pl) {
 }  // namespace
 
 int pk_rec4f_covers(int cell, int H) {
-    static int off = -1;
-    if (off < 0) {
-        const char* e = pk_experiment("rec_f32_gen4");  // 0 = keep the first-generation LSTM kernels / the step-wise GRU (A/B measurements)
-        off = (e && e[0] == '0') ? 1 : 0;
-    }
-    return !off && (cell == PK_CELL_LSTM || cell == PK_CELL_GRU || cell == PK_CELL_MINGRU) && H >= 1 && H <= KPAD;
+    // PK_EXPERIMENT rec_f32_gen4=0 keeps the first-generation LSTM kernels / the step-wise GRU (A/B measurements)
+    static const int on = pk_experiment_digit("rec_f32_gen4", 0, 0, 1);
+    return on && (cell == PK_CELL_LSTM || cell == PK_CELL_GRU || cell == PK_CELL_MINGRU) && H >= 1 && H <= KPAD;
 }
 // floats of exchange buffer one call needs: forward T*B rows x ndir*Hp (twice for the two-phase cells: h and r*h / z*h),
 // backward ndir*T*B rows x G*Hp (pitches rounded up to 16 floats); the larger of the two serves both passes
@@ -1141,87 +1115,45 @@ int64_t pk_rec4f_ln_work_floats(int T, int B, int bidir, int H) {
 int pk_rec4f_fwd(hipStream_t st, int cell, int act, int T, int B, int bidir, int H, const float* P, const float* pscale,
                  const float* pshift, const float* U, const float* mask, float mask_scalar, float* Y, float* S, float* Yx,
                  const PkLnHost* ln) {
-    int rc = pk_rec2_check("pk_rec_fwd (fp32, persistent, generation 4)", pk_rec4f_covers(cell, H), cell, T, B, bidir, H);
+    const char* who = "pk_rec_fwd (fp32, persistent, generation 4)";
+    int rc = pk_rec2_check(who, pk_rec4f_covers(cell, H), cell, T, B, bidir, H);
     if (rc) return rc;
-    const int ndir = 1 + bidir, R = B * ndir, Hp = (H + 7) & ~7;
+    const int ndir = 1 + bidir, Hp = (H + 7) & ~7;
     const bool two = pk_cell_two_phase(cell);
     const int64_t y_pitch = ((int64_t)ndir * Hp + 15) / 16 * 16;
     const size_t slab = (size_t)T * B * y_pitch * 4;
     PK_REQUIRE(((uintptr_t)Yx & 15) == 0, "pk_rec_fwd: exchange buffer must be 16-byte aligned");
     PK_REQUIRE((double)slab < 4.0e9, "pk_rec_fwd (fp32, persistent): exchange buffer exceeds the 4 GB buffer-descriptor range");
+    R2Args a{};
     Plan2 pl;
-    rc = make_plan4(R, H, pl);
+    rc = pk_rec2_prepare_fwd(a, pl, make_plan4, cell, act, T, B, bidir, H, y_pitch, P, pscale, pshift, U, mask, mask_scalar, Y, S);
     if (rc) return rc;
-    R2Args a;
-    a.T = T; a.B = B; a.R = R; a.H = H; a.Hp = Hp; a.YH = ndir * H; a.act = act;
-    a.C = pl.C; a.Pn = pl.Pn; a.rpc = pl.rpc; a.row0 = 0;
-    a.P = P; a.pscale = pscale; a.pshift = pshift; a.U = U; a.mask = mask; a.mask_scalar = mask_scalar;
-    a.Y = Y; a.S = S; a.Yb = nullptr; a.Xb = nullptr; a.Ypitch = (int)y_pitch;
-    a.dY = nullptr; a.dP2 = nullptr; a.dGb = nullptr; a.Gpitch = 0;
-    a.Yx = Yx; a.dGx = nullptr; a.Xx = two ? Yx + slab / 4 : nullptr;
-    rc = pk_rec2_host_setup(a, false, cell);
-    if (rc) return rc;
-    a.self_fill = self_fill4();
+    a.Yx = Yx; a.Xx = two ? Yx + slab / 4 : nullptr;
+    a.self_fill = pk_rec2_f32_self_fill();
     // the mailboxes: every dword "not written yet" - written by the kernel itself a few steps ahead of its publishes, or
     // (PK_EXPERIMENT rec4_self_fill=0) by one fill of 282 / 565 MB in front of the launches
     if (!a.self_fill) PK_CHECK_HIP(hipMemsetAsync(Yx, 0xFF, slab * (two ? 2 : 1), st));
-    rc = pk_rec2_ln_setup(st, a, pl, ln, false);
-    if (rc) return rc;
-    const size_t lds = lds4(cell, false, ln != nullptr);
-    const Rec4Kernel k = pick4(cell, act, false, ln != nullptr);
-    rc = grant_lds4(k, lds);
-    if (rc) return rc;
-    for (int l = 0; l < pl.launches; ++l) {
-        a.row0 = l * pl.C * pl.rpc;
-        a.ln_cg0 = l * pl.C;
-        rc = pk_rec2_reset_handshake(st, a);
-        if (rc) return rc;
-        rc = pk_rec2_check_residency((const void*)k, 256, lds, pl.C * pl.Pn, "pk_rec_fwd (fp32, persistent, generation 4)");
-        if (rc) return rc;
-        hipLaunchKernelGGL(k, dim3(pl.C * pl.Pn), dim3(256), lds, st, a);
-        PK_LAUNCH_CHECK();
-    }
-    return 0;
+    return pk_rec2_run(st, a, pl, cell, false, pick4(cell, act, false, ln != nullptr), 256, lds4(cell, false, ln != nullptr), who, ln,
+                       REC2_HELP_NONE);
 }
 
 int pk_rec4f_bwd(hipStream_t st, int cell, int act, int T, int B, int bidir, int H, const float* U, const float* mask,
                  float mask_scalar, const float* Y, const float* S, const float* dY, float* dP2, float* dGx, const PkLnHost* ln) {
-    int rc = pk_rec2_check("pk_rec_bwd (fp32, persistent, generation 4)", pk_rec4f_covers(cell, H), cell, T, B, bidir, H);
+    const char* who = "pk_rec_bwd (fp32, persistent, generation 4)";
+    int rc = pk_rec2_check(who, pk_rec4f_covers(cell, H), cell, T, B, bidir, H);
     if (rc) return rc;
-    const int ndir = 1 + bidir, R = B * ndir, Hp = (H + 7) & ~7, G = pk_cell_gates(cell);
+    const int ndir = 1 + bidir, Hp = (H + 7) & ~7, G = pk_cell_gates(cell);
     const int64_t g_pitch = ((int64_t)G * Hp + 15) / 16 * 16;
     const size_t bytes = (size_t)ndir * T * B * g_pitch * 4;
     PK_REQUIRE(((uintptr_t)dGx & 15) == 0, "pk_rec_bwd: exchange buffer must be 16-byte aligned");
     PK_REQUIRE((double)bytes < 4.0e9, "pk_rec_bwd (fp32, persistent): exchange buffer exceeds the 4 GB buffer-descriptor range");
+    R2Args a{};
     Plan2 pl;
-    rc = make_plan4(R, H, pl);
+    rc = pk_rec2_prepare_bwd(a, pl, make_plan4, cell, act, T, B, bidir, H, g_pitch, U, mask, mask_scalar, Y, S, dY, dP2);
     if (rc) return rc;
-    R2Args a;
-    a.T = T; a.B = B; a.R = R; a.H = H; a.Hp = Hp; a.YH = ndir * H; a.act = act;
-    a.C = pl.C; a.Pn = pl.Pn; a.rpc = pl.rpc; a.row0 = 0;
-    a.P = nullptr; a.pscale = nullptr; a.pshift = nullptr; a.U = U; a.mask = mask; a.mask_scalar = mask_scalar;
-    a.Y = const_cast<float*>(Y); a.S = const_cast<float*>(S); a.Yb = nullptr; a.Xb = nullptr; a.Ypitch = 0;
-    a.dY = dY; a.dP2 = dP2; a.dGb = nullptr; a.Gpitch = (int)g_pitch;
-    a.Yx = nullptr; a.dGx = dGx; a.Xx = nullptr;
-    rc = pk_rec2_host_setup(a, true, cell);
-    if (rc) return rc;
-    a.self_fill = self_fill4();
+    a.dGx = dGx;
+    a.self_fill = pk_rec2_f32_self_fill();
     if (!a.self_fill) PK_CHECK_HIP(hipMemsetAsync(dGx, 0xFF, bytes, st));
-    rc = pk_rec2_ln_setup(st, a, pl, ln, true);
-    if (rc) return rc;
-    const size_t lds = lds4(cell, true, ln != nullptr);
-    const Rec4Kernel k = pick4(cell, act, true, ln != nullptr);
-    rc = grant_lds4(k, lds);
-    if (rc) return rc;
-    for (int l = 0; l < pl.launches; ++l) {
-        a.row0 = l * pl.C * pl.rpc;
-        a.ln_cg0 = l * pl.C;
-        rc = pk_rec2_reset_handshake(st, a);
-        if (rc) return rc;
-        rc = pk_rec2_check_residency((const void*)k, 256, lds, pl.C * pl.Pn, "pk_rec_bwd (fp32, persistent, generation 4)");
-        if (rc) return rc;
-        hipLaunchKernelGGL(k, dim3(pl.C * pl.Pn), dim3(256), lds, st, a);
-        PK_LAUNCH_CHECK();
-    }
-    return pk_rec2_ln_finish(st, a, ln);
+    return pk_rec2_run(st, a, pl, cell, true, pick4(cell, act, true, ln != nullptr), 256, lds4(cell, true, ln != nullptr), who, ln,
+                       REC2_HELP_NONE);
 }
