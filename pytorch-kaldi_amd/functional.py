@@ -8,6 +8,7 @@ torch-op fallback: a CPU tensor or a missing library raises.
 import ctypes
 import os
 import weakref
+from typing import NamedTuple
 
 import torch
 
@@ -1618,6 +1619,125 @@ def choose_rec_algo(cell, H, use_ln):
     return REC_PERSISTENT if ok else REC_STEPWISE
 
 
+def perf_path_ok(cell, H, use_ln, use_bn, training):
+    """The bf16 pipeline (RecLayerPerfFn) covers liGRU / RNN / LSTM layers without per-step LayerNorm; BatchNorm
+    backward through frozen statistics (eval-mode module with autograd on) stays on the general path."""
+    if not bf16_mode() or settings.rec_algo == "stepwise":
+        return False
+    if cell not in ("liGRU", "RNN", "LSTM", "GRU", "minimalGRU") or H > 576 or use_ln:
+        return False
+    return training or not use_bn or not torch.is_grad_enabled()
+
+
+class RecRoute(NamedTuple):
+    """Where one recurrent layer runs: decided once, by rec_route."""
+    perf: bool   # RecLayerPerfFn (the bf16 pipeline) or RecLayerFn (the general node)
+    algo: int    # REC_STEPWISE / REC_PERSISTENT
+    family: str  # the library entries: "generic" (pk_rec_fwd / _bwd) or a key of _REC_BF16
+
+
+# the bf16 persistent recurrences (include/pk_amd.h): "2p" = the two-phase cells (GRU / minimalGRU, a second mailbox
+# Xb), "_ln" = per-step LayerNorm of h_t inside the time loop
+_REC_BF16 = {"bf16": "pk_rec_%s_bf16", "bf16_ln": "pk_rec_%s_bf16_ln", "2p_bf16": "pk_rec2p_%s_bf16", "2p_bf16_ln": "pk_rec2p_%s_bf16_ln"}
+
+
+def rec_route(cell, H, use_ln, use_bn, training):
+    """The node, the algorithm and the entry family of a layer.  The perf node runs persistent kernels only and never
+    asks choose_rec_algo (which raises under a forced "persistent" for the layers of the general node it cannot cover)."""
+    two_phase = cell in ("GRU", "minimalGRU")
+    if perf_path_ok(cell, H, use_ln, use_bn, training):
+        return RecRoute(True, REC_PERSISTENT, "2p_bf16" if two_phase else "bf16")
+    algo = choose_rec_algo(cell, H, use_ln)
+    if not bf16_mode() or algo != REC_PERSISTENT:
+        return RecRoute(False, algo, "generic")
+    return RecRoute(False, algo, ("2p_bf16_ln" if two_phase else "bf16_ln") if use_ln else "bf16")
+
+
+class RecCfg(NamedTuple):
+    """One recurrent layer as nn._Recurrent.forward describes it to RecLayerFn / RecLayerPerfFn (kept as ctx.cfg)."""
+    cell: str
+    act: str
+    H: int
+    bidir: bool
+    use_bn: bool
+    training: bool
+    eps: float
+    momentum: float
+    mask_scalar: float
+    xseg: tuple = None     # perf node: (segments, length, pitch) of the bf16 input handed over by the layer below
+    wparams: list = None   # the gates' parameters, and whether their gradients bypass autograd: weight-gradient GEMMs on
+    uparams: list = None   # the side stream that add into the flat .grad (the node then gets Wcat / Ucat detached)
+    side_w: bool = False
+    side_u: bool = False
+    bn_bufs: tuple = None  # perf node: per-gate (running_mean, running_var, num_batches_tracked) lists
+    # perf node: (gamma parameters, beta parameters) when the BatchNorm affine was handed over DETACHED (views of the flat
+    # buffer): backward adds d gamma / d beta to their flat .grad inside pk_bn_bwd_bf16 (`edge` keeps the node alive)
+    affine: tuple = None
+    keep_y: bool = True    # perf node, forward-only chunks: False = an inner layer whose fp32 output nobody reads
+    route: RecRoute = None
+
+
+# Sizes of one layer call, computed once in forward and kept as ctx.geom.  G gates, NS saved state slots per step; Hp: H
+# rounded up to 8, the pitch of a direction half / a gate in the bf16 exchange buffers Yb, Xb [T*B][y_pitch] and dGb
+# [ndir*T*B][g_pitch]
+_RecGeom = NamedTuple("_RecGeom", [(n, int) for n in "T B D G NS ndir TB GH Hp y_pitch g_pitch".split()])
+
+
+def _rec_geom(lib, cfg, shape):
+    T, B, D = shape
+    G, NS = lib.pk_rec_num_gates(CELL[cfg.cell]), lib.pk_rec_num_saved(CELL[cfg.cell])
+    ndir, Hp = 2 if cfg.bidir else 1, _up(cfg.H, 8)
+    return _RecGeom(T, B, D, G, NS, ndir, T * B, G * cfg.H, Hp, _up(ndir * Hp, 64), _up(G * Hp, 64))
+
+
+def _proj_scale_shift(cfg, P, mean, var, gamma, beta, running_mean, running_var, bcat):
+    """(mean, var, pscale, pshift) that turn the projections P [T*B, G*H] into gate pre-activations: BatchNorm (mean /
+    var: the batch statistics in training mode, replaced by the running ones otherwise) or the plain bias."""
+    if not cfg.use_bn:
+        pscale = torch.ones(P.shape[1], device=P.device)
+        return None, None, pscale, bcat.contiguous() if bcat is not None else torch.zeros(P.shape[1], device=P.device)
+    if cfg.training:
+        # duplicating every row leaves mean / biased var unchanged; only the unbiased running_var factor sees the
+        # reference's row count ndir*T*B
+        return (mean, var) + bn_finalize(mean, var, gamma, beta, cfg.eps, running_mean, running_var, cfg.momentum,
+                                         (2 if cfg.bidir else 1) * P.shape[0])
+    return (running_mean, running_var) + bn_finalize(running_mean, running_var, gamma, beta, cfg.eps)
+
+
+def _accumulate_gate_rows(params, d, G, H):
+    _accumulate_rows(params, [d[g * H:(g + 1) * H] for g in range(G)])
+
+
+def _rec_bf16_fwd(lib, cfg, geom, P, pscale, pshift, Ucat, mask, Y, S, Yb, prefilled, Xb=None, ln=None):
+    """The forward entry of cfg.route.family, arguments in the order of include/pk_amd.h.  Xb: the two-phase families'
+    second mailbox; ln = (ln_gamma, ln_beta, LNS, lnwork): the _ln families."""
+    name = _REC_BF16[cfg.route.family] % "fwd"
+    a = [_stream(), CELL[cfg.cell], ACT[cfg.act], geom.T, geom.B, int(cfg.bidir), cfg.H, _p(P), _p(pscale), _p(pshift),
+         _p(Ucat), _p(mask), float(cfg.mask_scalar)]
+    if ln is not None:
+        a += [_p(ln[0]), _p(ln[1]), LN_EPS]
+    a += [_p(Y), _p(S)] + ([_p(ln[2])] if ln is not None else []) + [_p(Yb)]
+    if cfg.route.family.startswith("2p"):
+        a.append(_p(Xb))
+    a += [geom.y_pitch, prefilled] + ([_p(ln[3])] if ln is not None else [])
+    _lib.check(getattr(lib, name)(*a), name)
+
+
+def _rec_bf16_bwd(lib, cfg, geom, Ucat, mask, Y, S, dY, dP2, dGb, prefilled, ln=None):
+    """The backward entry of cfg.route.family.  dP2 (fp32 gate gradients, may be None): not an argument of the two-phase
+    entries, whose gate gradients come back as bf16 only; ln = (ln_gamma, LNS, lnwork, dlg, dlb): the _ln families."""
+    name = _REC_BF16[cfg.route.family] % "bwd"
+    a = [_stream(), CELL[cfg.cell], ACT[cfg.act], geom.T, geom.B, int(cfg.bidir), cfg.H, _p(Ucat), _p(mask),
+         float(cfg.mask_scalar)]
+    if ln is not None:
+        a += [_p(ln[0]), LN_EPS]
+    a += [_p(Y), _p(S)] + ([_p(ln[1])] if ln is not None else []) + [_p(dY)]
+    if not cfg.route.family.startswith("2p"):
+        a.append(_p(dP2))
+    a += [_p(dGb), geom.g_pitch, prefilled] + ([_p(x) for x in ln[2:]] if ln is not None else [])
+    _lib.check(getattr(lib, name)(*a), name)
+
+
 _DU_SPLITK = 16  # pk_rec.hip DU_SPLITK: the same split of the reduction (pk_gemm clamps it to 32-deep slices), so the same sums
 
 
@@ -1733,20 +1853,11 @@ class RecLayerFn(torch.autograd.Function):
     def forward(ctx, x, Wcat, bcat, Ucat, gamma, beta, running_mean, running_var, mask, ln_gamma, ln_beta, cfg):
         _need_gpu(x, Wcat, bcat, Ucat, gamma, beta, mask, ln_gamma, ln_beta)
         lib = _lib.load()
-        cell, act, H, bidir, use_bn, training, eps, momentum, mask_scalar = cfg[:9]
-        # (round 6) the gates' parameters and whether their gradients bypass autograd: exact-fp32 weight-gradient GEMMs on
-        # the side stream, accumulating into the flat .grad (decided by nn._Recurrent.forward, which then hands Wcat / Ucat
-        # over detached)
-        ctx.wparams, ctx.uparams = (cfg[9], cfg[10]) if len(cfg) > 10 else (None, None)
-        ctx.side_w, ctx.side_u = (bool(cfg[11]), bool(cfg[12])) if len(cfg) > 12 else (False, False)
-        T, B, D = x.shape
+        geom = _rec_geom(lib, cfg, x.shape)
+        route, H = cfg.route, cfg.H
+        T, B, D, TB, GH = geom.T, geom.B, geom.D, geom.TB, geom.GH
         x2 = _rows2d(x)
-        G = lib.pk_rec_num_gates(CELL[cell])
-        NS = lib.pk_rec_num_saved(CELL[cell])
-        ndir = 2 if bidir else 1
-        TB, GH = T * B, G * H
-        Wcat = Wcat.contiguous()
-        Ucat = Ucat.contiguous()
+        Wcat, Ucat = Wcat.contiguous(), Ucat.contiguous()
         # K1: input projections for all steps at once, on the NON-duplicated batch (the reversed
         # half of the reference's cat([x, flip(x)]) is the same rows read backwards in time)
         P = _new(TB, GH, like=x2)
@@ -1757,78 +1868,46 @@ class RecLayerFn(torch.autograd.Function):
             gemm_bf16(TB, GH, D, xb, xb.shape[1], 1, Wb, Wb.shape[1], 1, P, GH)
         else:
             gemm(TB, GH, D, x2, x2.stride(0), 1, Wcat, 1, D, P, GH)
-        mean = var = None
-        if use_bn:
-            if training:
-                mean, var = bn_stats(P)
-                # duplicating every row leaves mean / biased var unchanged; only the unbiased
-                # running_var factor sees the reference's row count ndir*T*B
-                pscale, pshift = bn_finalize(mean, var, gamma, beta, eps, running_mean, running_var, momentum, ndir * TB)
-            else:
-                mean, var = running_mean, running_var
-                pscale, pshift = bn_finalize(mean, var, gamma, beta, eps)
-        else:
-            pscale = torch.ones(GH, device=x.device)
-            pshift = bcat.contiguous() if bcat is not None else torch.zeros(GH, device=x.device)
-        Y = _new(T, B, ndir * H, like=x2)
-        S = _new(ndir, TB, NS * H, like=x2)
+        mean, var = bn_stats(P) if cfg.use_bn and cfg.training else (None, None)
+        mean, var, pscale, pshift = _proj_scale_shift(cfg, P, mean, var, gamma, beta, running_mean, running_var, bcat)
+        Y = _new(T, B, geom.ndir * H, like=x2)
+        S = _new(geom.ndir, TB, geom.NS * H, like=x2)
         use_ln = ln_gamma is not None
-        algo = choose_rec_algo(cell, H, use_ln)
         prec = PREC[settings.precision]
-        if algo == REC_PERSISTENT:
+        if route.algo == REC_PERSISTENT:
             _lib.raise_if_persist_failed()
-        LNS = None
-        n_work = int(lib.pk_rec_work_floats(CELL[cell], T, B, int(bidir), H))
-        n_lnwork = 0
+        LNS, n_lnwork = None, 0
+        n_work = int(lib.pk_rec_work_floats(CELL[cfg.cell], T, B, int(cfg.bidir), H))
         if use_ln:  # per-step LayerNorm of h_t: statistics and pre-LN h of every (step, row), saved for backward
             ln_gamma, ln_beta = ln_gamma.contiguous(), ln_beta.contiguous()
-            LNS = _new(int(lib.pk_rec_ln_saved_floats(T, B, int(bidir), H)), like=x2)
-            if algo == REC_PERSISTENT:  # + the row-statistics exchange of the persistent kernels
-                n_lnwork = int(lib.pk_rec_ln_work_floats(T, B, int(bidir), H))
+            LNS = _new(int(lib.pk_rec_ln_saved_floats(T, B, int(cfg.bidir), H)), like=x2)
+            if route.algo == REC_PERSISTENT:  # + the row-statistics exchange of the persistent kernels
+                n_lnwork = int(lib.pk_rec_ln_work_floats(T, B, int(cfg.bidir), H))
         work = _new(n_work + (0 if bf else n_lnwork), like=x2)
-        Yb = None
-        ctx.Xb = None
-        if bf and algo == REC_PERSISTENT:
+        Yb = Xb = None
+        if route.family != "generic":
             # perf mode: second-generation persistent kernel; its bf16 exchange buffer Yb is also the
             # k-major operand of the dU GEMM in backward (nothing is converted afterwards)
-            Hp = _up(H, 8)
-            Yb = torch.empty(TB, _up(ndir * Hp, 64), device=x.device, dtype=torch.bfloat16)
-            two_phase = cell in ("GRU", "minimalGRU")
-            if use_ln and two_phase:
-                lnwork = _new(n_lnwork, like=x2)
-                ctx.Xb = torch.empty_like(Yb)  # second mailbox of the two-phase cells: r*h (GRU) / z*h (minimalGRU)
-                rc = lib.pk_rec2p_fwd_bf16_ln(_stream(), CELL[cell], ACT[act], T, B, int(bidir), H, _p(P), _p(pscale),
-                                              _p(pshift), _p(Ucat), _p(mask), float(mask_scalar), _p(ln_gamma), _p(ln_beta),
-                                              LN_EPS, _p(Y), _p(S), _p(LNS), _p(Yb), _p(ctx.Xb), Yb.shape[1],
-                                              2 if settings.self_fill else 0, _p(lnwork))
-            elif use_ln:
-                lnwork = _new(n_lnwork, like=x2)
-                rc = lib.pk_rec_fwd_bf16_ln(_stream(), CELL[cell], ACT[act], T, B, int(bidir), H, _p(P), _p(pscale),
-                                            _p(pshift), _p(Ucat), _p(mask), float(mask_scalar), _p(ln_gamma), _p(ln_beta),
-                                            LN_EPS, _p(Y), _p(S), _p(LNS), _p(Yb), Yb.shape[1],
-                                            2 if settings.self_fill else 0, _p(lnwork))
-            else:
-                rc = lib.pk_rec_fwd_bf16(_stream(), CELL[cell], ACT[act], T, B, int(bidir), H, _p(P), _p(pscale),
-                                         _p(pshift), _p(Ucat), _p(mask), float(mask_scalar), _p(Y), _p(S), _p(Yb),
-                                         Yb.shape[1], 2 if settings.self_fill else 0)
-            _lib.check(rc, "pk_rec_fwd_bf16")
+            Yb = torch.empty(TB, geom.y_pitch, device=x.device, dtype=torch.bfloat16)
+            ln = (ln_gamma, ln_beta, LNS, _new(n_lnwork, like=x2)) if use_ln else None
+            if route.family.startswith("2p"):
+                Xb = torch.empty_like(Yb)  # second mailbox of the two-phase cells: r*h (GRU) / z*h (minimalGRU)
+            _rec_bf16_fwd(lib, cfg, geom, P, pscale, pshift, Ucat, mask, Y, S, Yb, 2 if settings.self_fill else 0, Xb, ln)
         else:
-            rc = lib.pk_rec_fwd(_stream(), algo, prec, CELL[cell], ACT[act], T, B, int(bidir), H, _p(P), _p(pscale),
-                                _p(pshift), _p(Ucat), _p(mask), float(mask_scalar), _p(ln_gamma), _p(ln_beta), _p(Y),
-                                _p(S), _p(LNS), _p(work))
+            rc = lib.pk_rec_fwd(_stream(), route.algo, prec, CELL[cfg.cell], ACT[cfg.act], T, B, int(cfg.bidir), H, _p(P),
+                                _p(pscale), _p(pshift), _p(Ucat), _p(mask), float(cfg.mask_scalar), _p(ln_gamma), _p(ln_beta),
+                                _p(Y), _p(S), _p(LNS), _p(work))
             _lib.check(rc, "pk_rec_fwd")
-        _force_kinks(S, cell, T, B, ndir, H)
-        ctx.bf = bf
-        ctx.Yb = Yb
+        _force_kinks(S, cfg.cell, T, B, geom.ndir, H)
+        ctx.bf, ctx.prec, ctx.work_floats = bf, prec, (n_work, n_lnwork)
+        ctx.Yb, ctx.Xb = Yb, Xb
         if bf:
             ctx.save_for_backward(xb, Wb, Ucat, P, mean, var, gamma, mask, Y, S, pscale, ln_gamma, LNS)
         else:
             ctx.save_for_backward(x2, Wcat, Ucat, P, mean, var, gamma, mask, Y, S, pscale, ln_gamma, LNS)
-        ctx.cfg = cfg[:9]
-        ctx.algo, ctx.prec = algo, prec
-        ctx.in_shape = x.shape
+        ctx.cfg, ctx.geom = cfg, geom
         ctx.has_bias = bcat is not None
-        if use_bn and training:
+        if cfg.use_bn and cfg.training:
             ctx.mark_non_differentiable(mean, var)
             return Y, mean, var
         return Y, None, None
@@ -1837,72 +1916,50 @@ class RecLayerFn(torch.autograd.Function):
     def backward(ctx, dY, _dm, _dv):
         lib = _lib.load()
         x2, Wcat, Ucat, P, mean, var, gamma, mask, Y, S, pscale, ln_gamma, LNS = ctx.saved_tensors
-        cell, act, H, bidir, use_bn, training, eps, momentum, mask_scalar = ctx.cfg
-        T, B, D = ctx.in_shape
-        G = lib.pk_rec_num_gates(CELL[cell])
-        ndir = 2 if bidir else 1
-        TB, GH = T * B, G * H
+        cfg, geom, bf = ctx.cfg, ctx.geom, ctx.bf
+        route, cell, H, use_bn, eps = cfg.route, cfg.cell, cfg.H, cfg.use_bn, cfg.eps
+        T, B, D, G, ndir, TB, GH = geom.T, geom.B, geom.D, geom.G, geom.ndir, geom.TB, geom.GH
         dY = dY.contiguous()
         dP2 = _new(ndir, TB, GH, like=dY)
         dU = _new(GH, H, like=dY)
-        bf = ctx.bf
-        n_lnwork = 0
-        if ln_gamma is not None and ctx.algo == REC_PERSISTENT:
-            n_lnwork = int(lib.pk_rec_ln_work_floats(T, B, int(bidir), H))
-        work = _new(int(lib.pk_rec_work_floats(CELL[cell], T, B, int(bidir), H)) + (0 if ctx.Yb is not None else n_lnwork),
-                    like=dY)
+        n_work, n_lnwork = ctx.work_floats  # (as in forward: the row-statistics exchange of persistent LayerNorm layers)
+        work = _new(n_work + (n_lnwork if route.family == "generic" else 0), like=dY)
         dlg = dlb = None
         if ln_gamma is not None:
             dlg, dlb = _new(H, like=dY), _new(H, like=dY)
         dGb = None
-        if ctx.Yb is not None:
-            Hp = _up(H, 8)
-            dGb = torch.empty(ndir * TB, _up(G * Hp, 64), device=dY.device, dtype=torch.bfloat16)
-            if ctx.Xb is not None:  # two-phase cells (with per-step LayerNorm): the gate gradients come back as bf16 only
-                lnwork = _new(n_lnwork, like=dY)
-                rc = lib.pk_rec2p_bwd_bf16_ln(_stream(), CELL[cell], ACT[act], T, B, int(bidir), H, _p(Ucat), _p(mask),
-                                              float(mask_scalar), _p(ln_gamma), LN_EPS, _p(Y), _p(S), _p(LNS), _p(dY),
-                                              _p(dGb), dGb.shape[1], 2 if settings.self_fill else 0, _p(lnwork),
-                                              _p(dlg), _p(dlb))
+        if route.family != "generic":
+            dGb = torch.empty(ndir * TB, geom.g_pitch, device=dY.device, dtype=torch.bfloat16)
+            ln = (ln_gamma, LNS, _new(n_lnwork, like=dY), dlg, dlb) if ln_gamma is not None else None
+            _rec_bf16_bwd(lib, cfg, geom, Ucat, mask, Y, S, dY, dP2, dGb, 2 if settings.self_fill else 0, ln)
+            if route.family.startswith("2p"):  # two-phase cells (with per-step LayerNorm): the gate gradients come back as bf16 only
                 flat = dP2.view(ndir * TB, GH)
                 for g_ in range(G):
-                    flat[:, g_ * H:(g_ + 1) * H].copy_(dGb[:, g_ * Hp:g_ * Hp + H])
-            elif ln_gamma is not None:
-                lnwork = _new(n_lnwork, like=dY)
-                rc = lib.pk_rec_bwd_bf16_ln(_stream(), CELL[cell], ACT[act], T, B, int(bidir), H, _p(Ucat), _p(mask),
-                                            float(mask_scalar), _p(ln_gamma), LN_EPS, _p(Y), _p(S), _p(LNS), _p(dY),
-                                            _p(dP2), _p(dGb), dGb.shape[1], 2 if settings.self_fill else 0, _p(lnwork),
-                                            _p(dlg), _p(dlb))
-            else:
-                rc = lib.pk_rec_bwd_bf16(_stream(), CELL[cell], ACT[act], T, B, int(bidir), H, _p(Ucat), _p(mask),
-                                         float(mask_scalar), _p(Y), _p(S), _p(dY), _p(dP2), _p(dGb), dGb.shape[1],
-                                         2 if settings.self_fill else 0)
-            _lib.check(rc, "pk_rec_bwd_bf16")
+                    flat[:, g_ * H:(g_ + 1) * H].copy_(dGb[:, g_ * geom.Hp:g_ * geom.Hp + H])
         else:
-            side_u = (not bf) and ctx.side_u and side_targets_any_ok(ctx.uparams)
+            side_u = (not bf) and cfg.side_u and side_targets_any_ok(cfg.uparams)
             flush_deferred_side()  # (the output layers' postponed weight gradients: next to this recurrence)
-            rc = lib.pk_rec_bwd(_stream(), ctx.algo, ctx.prec, CELL[cell], ACT[act], T, B, int(bidir), H, _p(Ucat),
-                                _p(mask), float(mask_scalar), _p(ln_gamma), _p(Y), _p(S), _p(LNS), _p(dY), _p(dP2),
-                                None if (bf or ctx.side_u) else _p(dU), _p(dlg), _p(dlb), _p(work))
+            rc = lib.pk_rec_bwd(_stream(), route.algo, ctx.prec, CELL[cell], ACT[cfg.act], T, B, int(cfg.bidir), H, _p(Ucat),
+                                _p(mask), float(cfg.mask_scalar), _p(ln_gamma), _p(Y), _p(S), _p(LNS), _p(dY), _p(dP2),
+                                None if (bf or cfg.side_u) else _p(dU), _p(dlg), _p(dlb), _p(work))
             _lib.check(rc, "pk_rec_bwd")
-            if ctx.side_u and not side_u:  # (decided in forward, no longer possible: the gradient goes back through autograd... which has no edge)
+            if cfg.side_u and not side_u:  # (decided in forward, no longer possible: the gradient goes back through autograd... which has no edge)
                 raise _lib.PkError("recurrent layer: the flat gradient buffer the weights' gradients were to be added to is gone "
                                    "between forward and backward (optim.FlatParams.zero_grad() re-aliases it)")
-        NS_ = lib.pk_rec_num_saved(CELL[cell])
 
         def do_dU_f32():
-            gview = adjacent_view([q.grad for q in ctx.uparams])
+            gview = adjacent_view([q.grad for q in cfg.uparams])
             if gview is not None:
-                _deferred_dU_f32(cell, T, B, ndir, H, G, NS_, Y, S, dP2, gview, True)
+                _deferred_dU_f32(cell, T, B, ndir, H, G, geom.NS, Y, S, dP2, gview, True)
             else:
-                _deferred_dU_f32(cell, T, B, ndir, H, G, NS_, Y, S, dP2, dU, False)
-                _accumulate_rows(ctx.uparams, [dU[g * H:(g + 1) * H] for g in range(G)])
+                _deferred_dU_f32(cell, T, B, ndir, H, G, geom.NS, Y, S, dP2, dU, False)
+                _accumulate_gate_rows(cfg.uparams, dU, G, H)
 
         if bf:
             _deferred_dU_bf16(lib, cell, T, B, ndir, H, G, Y, S, dP2, dU, ctx.Yb, dGb, ctx.Xb)
             ctx.Yb = ctx.Xb = None
         g1 = dP2[0]
-        g2 = dP2[1] if bidir else None
+        g2 = dP2[1] if cfg.bidir else None
         dgamma = dbeta = dbias = None
         # the projection gradient is the operand of the dX / dW GEMMs: with BatchNorm (whose backward writes it at any pitch)
         # a row of 3 x 550 = 1650 floats - the GRU - is laid out at 1652, so that rows start 16-byte aligned and the products
@@ -1917,7 +1974,7 @@ class RecLayerFn(torch.autograd.Function):
             _lib.check(lib.pk_bn_bwd_reduce(_stream(), _p(g1), _p(g2), GH, _p(P), GH, TB, GH, _p(mean), _p(var), eps,
                                             _p(part), _p(sum_g), _p(sum_gx)), "pk_bn_bwd_reduce")
             dgamma, dbeta = sum_gx, sum_g
-            if training:
+            if cfg.training:
                 _lib.check(lib.pk_bn_bwd_apply(_stream(), _p(g1), _p(g2), GH, _p(P), GH, TB, GH, _p(mean), _p(var), eps,
                                                _p(gamma), _p(sum_g), _p(sum_gx), float(TB), _p(dPraw), ldp),
                            "pk_bn_bwd_apply")
@@ -1953,36 +2010,26 @@ class RecLayerFn(torch.autograd.Function):
             dx = dx.view(T, B, D)
         # weight gradients are off the dependency chain (next on it: the recurrence of the layer below, which leaves 112 CUs
         # idle): with flat-bucket parameters they run on the side stream, behind the dX GEMM, and add straight into .grad
-        side_w = ctx.side_w and side_targets_any_ok(ctx.wparams)
-        if ctx.side_w and not side_w:
+        side_w = cfg.side_w and side_targets_any_ok(cfg.wparams)
+        if cfg.side_w and not side_w:
             raise _lib.PkError("recurrent layer: the flat gradient buffer of the input weights is gone between forward and backward")
-        if ctx.side_u:
-            side_launch(do_dU_f32, (Y, S, dP2, dU), ctx.uparams)
+        if cfg.side_u:
+            side_launch(do_dU_f32, (Y, S, dP2, dU), cfg.uparams)
 
         def do_dW_f32():
-            gview = adjacent_view([q.grad for q in ctx.wparams])
+            gview = adjacent_view([q.grad for q in cfg.wparams])
             sk = _splitk(_tiles(GH, D), TB)
             if gview is not None:
                 gemm(GH, D, TB, dPraw, 1, ldp, x2, x2.stride(0), 1, gview, D, beta=1.0, splitk=sk)
             else:
                 gemm(GH, D, TB, dPraw, 1, ldp, x2, x2.stride(0), 1, dW, D, splitk=sk)
-                _accumulate_rows(ctx.wparams, [dW[g * H:(g + 1) * H] for g in range(G)])
+                _accumulate_gate_rows(cfg.wparams, dW, G, H)
 
         if side_w:
-            side_launch(do_dW_f32, (dPraw, x2, dW), ctx.wparams)
+            side_launch(do_dW_f32, (dPraw, x2, dW), cfg.wparams)
         else:
             gemm(GH, D, TB, dPraw, 1, ldp, x2, x2.stride(0), 1, dW, D, splitk=_splitk(_tiles(GH, D), TB))
-        return (dx, None if side_w else dW, dbias, None if ctx.side_u else dU, dgamma, dbeta, None, None, None, dlg, dlb, None)
-
-
-def perf_path_ok(cell, H, use_ln, use_bn, training):
-    """The bf16 pipeline below covers liGRU / RNN / LSTM layers without per-step LayerNorm; BatchNorm
-    backward through frozen statistics (eval-mode module with autograd on) stays on the general path."""
-    if not bf16_mode() or settings.rec_algo == "stepwise":
-        return False
-    if cell not in ("liGRU", "RNN", "LSTM", "GRU", "minimalGRU") or H > 576 or use_ln:
-        return False
-    return training or not use_bn or not torch.is_grad_enabled()
+        return (dx, None if side_w else dW, dbias, None if cfg.side_u else dU, dgamma, dbeta, None, None, None, dlg, dlb, None)
 
 
 class _Prefill:
@@ -2033,23 +2080,15 @@ class RecLayerPerfFn(torch.autograd.Function):
         ctx.set_materialize_grads(False)  # no 147 MB zero tensor for the (non-differentiable) bf16 twin in backward
         _need_gpu(x, Wcat, bcat, Ucat, gamma, beta, mask)
         lib = _lib.load()
-        cell, act, H, bidir, use_bn, training, eps, momentum, mask_scalar, xseg = cfg[:10]
-        ctx.wparams, ctx.uparams = (cfg[10], cfg[11]) if len(cfg) > 10 else (None, None)
-        ctx.side_w, ctx.side_u = (bool(cfg[12]), bool(cfg[13])) if len(cfg) > 13 else (False, False)
-        # (gamma parameters, beta parameters) when the BatchNorm affine was handed over DETACHED (views of the flat
-        # buffer): backward adds d gamma / d beta to their flat .grad inside pk_bn_bwd_bf16 (`edge` keeps the node alive)
-        ctx.affine = cfg[15] if len(cfg) > 15 else None
-        T, B, D = x.shape
-        G = lib.pk_rec_num_gates(CELL[cell])
-        NS = lib.pk_rec_num_saved(CELL[cell])
-        ndir = 2 if bidir else 1
-        TB, GH = T * B, G * H
-        Wcat = Wcat.contiguous()
-        Ucat = Ucat.contiguous()
+        geom = _rec_geom(lib, cfg, x.shape)
+        H, bn_train = cfg.H, cfg.use_bn and cfg.training
+        T, B, D, ndir, TB, GH = geom.T, geom.B, geom.D, geom.ndir, geom.TB, geom.GH
+        Wcat, Ucat = Wcat.contiguous(), Ucat.contiguous()
         if xb_in is None:
             xseg = None
             xb, Wb, K = cvt_bf16(_rows2d(x)), cvt_bf16(Wcat), D
         else:
+            xseg = cfg.xseg
             nseg, seglen, segpad = xseg
             assert nseg * seglen == D and xb_in.shape[0] == TB
             xb, Wb, K = xb_in, cvt_bf16(Wcat, nseg, seglen, segpad), nseg * segpad
@@ -2057,73 +2096,49 @@ class RecLayerPerfFn(torch.autograd.Function):
         # the kernels' bf16 exchange buffers must hold the 0xFF "not written yet" pattern: they are filled on a third
         # stream next to the projection GEMM / BatchNorm statistics instead of in front of the recurrence (the backward
         # one, dGb, too: 295 MB that would otherwise be filled on the critical path of backward)
-        Hp = _up(H, 8)
-        Yb = torch.empty(TB, _up(ndir * Hp, 64), device=x.device, dtype=torch.bfloat16)
-        two_phase = cell in ("GRU", "minimalGRU")
+        Yb = torch.empty(TB, geom.y_pitch, device=x.device, dtype=torch.bfloat16)
         # (the liGRU / RNN kernels write the pattern themselves, a few steps ahead of their own publishes: prefilled = 2)
-        self_fill = settings.self_fill and lib.pk_rec_self_fill(CELL[cell]) == 1
+        self_fill = settings.self_fill and lib.pk_rec_self_fill(CELL[cfg.cell]) == 1
         dGb = None
         if any(ctx.needs_input_grad) and not self_fill:  # a backward pass will follow: its exchange buffer is filled now
-            dGb = torch.empty(ndir * TB, _up(G * Hp, 64), device=x.device, dtype=torch.bfloat16)
-        Xb = torch.empty_like(Yb) if two_phase else None  # two exchanges per step: h and r*h (z*h)
+            dGb = torch.empty(ndir * TB, geom.g_pitch, device=x.device, dtype=torch.bfloat16)
+        Xb = torch.empty_like(Yb) if cfg.route.family.startswith("2p") else None  # two exchanges per step: h and r*h (z*h)
         fill = _Prefill()
         if not self_fill:
             fill.start(Yb, Xb, dGb)
         P = _new(TB, GH, like=Wcat)
-        mean = var = None
-        bn_bufs = cfg[14] if len(cfg) > 14 else None  # per-gate (running_mean, running_var, num_batches_tracked) lists
-        pscale = pshift = None
-        if use_bn and training and bn_bufs is not None:
+        mean = var = pscale = pshift = None
+        if bn_train and cfg.bn_bufs is not None:
             # the statistics come out of the projection GEMM's epilogue; their merge, scale / shift and the running
             # statistics of every gate's module are one launch behind it
             mean, var, pscale, pshift = gemm_bf16_bn_stats(TB, GH, K, xb, xb.shape[1], 1, Wb, Wb.shape[1], 1, P, GH, gates=(
-                gamma, beta, eps, H, bn_bufs[0], bn_bufs[1], bn_bufs[2], momentum, ndir * TB))
-        elif use_bn and training:
+                gamma, beta, cfg.eps, H, cfg.bn_bufs[0], cfg.bn_bufs[1], cfg.bn_bufs[2], cfg.momentum, ndir * TB))
+        elif bn_train:
             mean, var = gemm_bf16_bn_stats(TB, GH, K, xb, xb.shape[1], 1, Wb, Wb.shape[1], 1, P, GH)
         else:
             gemm_bf16(TB, GH, K, xb, xb.shape[1], 1, Wb, Wb.shape[1], 1, P, GH)
-        if use_bn:
-            if pscale is not None:
-                pass
-            elif training:
-                pscale, pshift = bn_finalize(mean, var, gamma, beta, eps, running_mean, running_var, momentum, ndir * TB)
-            else:
-                mean, var = running_mean, running_var
-                pscale, pshift = bn_finalize(mean, var, gamma, beta, eps)
-        else:
-            pscale = torch.ones(GH, device=x.device)
-            pshift = bcat.contiguous() if bcat is not None else torch.zeros(GH, device=x.device)
+        if pscale is None:
+            mean, var, pscale, pshift = _proj_scale_shift(cfg, P, mean, var, gamma, beta, running_mean, running_var, bcat)
         # A validation / forward chunk (torch.no_grad, core.py:644-671: nothing here needs a gradient) saves nothing for a
         # backward pass: no S (563 MB per Li-GRU layer at the BASELINE shape), and an INNER layer of a stack does not write
-        # its fp32 output either - the next layer reads the bf16 copy Yb (cfg[16], set by nn._Recurrent.forward; the
+        # its fp32 output either - the next layer reads the bf16 copy Yb (cfg.keep_y, set by nn._Recurrent.forward; the
         # tensor returned in its place carries the shape only).
         infer = not any(ctx.needs_input_grad) and _Kinks.queue is None and _lib.experiment("fwd_nosave", "1") != "0"
-        keep_y = bool(cfg[16]) if len(cfg) > 16 else True
         Y = _new(T, B, ndir * H, like=Wcat)
-        S = None if infer else _new(ndir, TB, NS * H, like=Wcat)
-        Yarg = Y if (keep_y or not infer) else None
+        S = None if infer else _new(ndir, TB, geom.NS * H, like=Wcat)
+        Yarg = Y if (cfg.keep_y or not infer) else None
         _lib.raise_if_persist_failed()
         fill.wait()
-        if two_phase:
-            rc = lib.pk_rec2p_fwd_bf16(_stream(), CELL[cell], ACT[act], T, B, int(bidir), H, _p(P), _p(pscale),
-                                       _p(pshift), _p(Ucat), _p(mask), float(mask_scalar), _p(Yarg), _p(S), _p(Yb), _p(Xb),
-                                       Yb.shape[1], 2 if self_fill else fill.done)
-            _lib.check(rc, "pk_rec2p_fwd_bf16")
-        else:
-            rc = lib.pk_rec_fwd_bf16(_stream(), CELL[cell], ACT[act], T, B, int(bidir), H, _p(P), _p(pscale), _p(pshift),
-                                     _p(Ucat), _p(mask), float(mask_scalar), _p(Yarg), _p(S), _p(Yb), Yb.shape[1],
-                                     2 if self_fill else fill.done)
-            _lib.check(rc, "pk_rec_fwd_bf16")
+        _rec_bf16_fwd(lib, cfg, geom, P, pscale, pshift, Ucat, mask, Yarg, S, Yb, 2 if self_fill else fill.done, Xb)
         if S is not None:
-            _force_kinks(S, cell, T, B, ndir, H)
+            _force_kinks(S, cfg.cell, T, B, ndir, H)
         ctx.self_fill = self_fill
         ctx.dGb = dGb if fill.done else None
         ctx.Xb = Xb
         ctx.save_for_backward(xb, Wb, Wcat, Ucat, P, mean, var, gamma, mask, Y, S, Yb)
-        ctx.cfg = cfg[:9] + (xseg,)
-        ctx.in_shape = x.shape
+        ctx.cfg, ctx.geom, ctx.xseg = cfg, geom, xseg
         ctx.has_bias = bcat is not None
-        if use_bn and training:
+        if bn_train:
             ctx.mark_non_differentiable(mean, var, Yb)
             return Y, mean, var, Yb
         ctx.mark_non_differentiable(Yb)
@@ -2135,33 +2150,22 @@ class RecLayerPerfFn(torch.autograd.Function):
             return (None,) * 12
         lib = _lib.load()
         xb, Wb, Wcat, Ucat, P, mean, var, gamma, mask, Y, S, Yb = ctx.saved_tensors
-        cell, act, H, bidir, use_bn, training, eps, momentum, mask_scalar, xseg = ctx.cfg
-        if use_bn and not training:
+        cfg, geom, xseg = ctx.cfg, ctx.geom, ctx.xseg
+        cell, H, use_bn = cfg.cell, cfg.H, cfg.use_bn
+        if use_bn and not cfg.training:
             raise _lib.PkError("perf-mode recurrent layer: backward through frozen BatchNorm statistics is not covered")
-        T, B, D = ctx.in_shape
-        G = lib.pk_rec_num_gates(CELL[cell])
-        ndir = 2 if bidir else 1
-        TB, GH = T * B, G * H
-        Hp = _up(H, 8)
+        T, B, D, G, ndir, TB, GH, Gp = geom.T, geom.B, geom.D, geom.G, geom.ndir, geom.TB, geom.GH, geom.g_pitch
         dY = dY.contiguous()
         dGb, prefilled = ctx.dGb, 1  # filled with the "not written" pattern during forward (third stream)
         ctx.dGb = None
         if dGb is None:
-            dGb = torch.empty(ndir * TB, _up(G * Hp, 64), device=dY.device, dtype=torch.bfloat16)
+            dGb = torch.empty(ndir * TB, Gp, device=dY.device, dtype=torch.bfloat16)
             prefilled = 2 if ctx.self_fill else 0
-        Gp = dGb.shape[1]
         flush_deferred_side()  # the output layers' weight gradients: ready when this recurrence is, next to it on the idle CUs
-        if ctx.Xb is not None:
-            rc = lib.pk_rec2p_bwd_bf16(_stream(), CELL[cell], ACT[act], T, B, int(bidir), H, _p(Ucat), _p(mask),
-                                       float(mask_scalar), _p(Y), _p(S), _p(dY), _p(dGb), Gp, prefilled)
-            _lib.check(rc, "pk_rec2p_bwd_bf16")
-        else:
-            rc = lib.pk_rec_bwd_bf16(_stream(), CELL[cell], ACT[act], T, B, int(bidir), H, _p(Ucat), _p(mask),
-                                     float(mask_scalar), _p(Y), _p(S), _p(dY), None, _p(dGb), Gp, prefilled)
-            _lib.check(rc, "pk_rec_bwd_bf16")
+        _rec_bf16_bwd(lib, cfg, geom, Ucat, mask, Y, S, dY, None, dGb, prefilled)
         # weight gradients are off the dependency chain (the next thing on it is the layer below's recurrent
         # backward): with flat-bucket parameters they run on the side stream and accumulate straight into .grad
-        side_u, side_w = ctx.side_u, ctx.side_w  # decided in forward: those weights were handed over detached
+        side_u, side_w = cfg.side_u, cfg.side_w  # decided in forward: those weights were handed over detached
         Xb = ctx.Xb
         ctx.Xb = None
         dU = _new(GH, H, like=dY)
@@ -2169,13 +2173,13 @@ class RecLayerPerfFn(torch.autograd.Function):
         def do_dU():
             _deferred_dU_bf16(lib, cell, T, B, ndir, H, G, Y, S, None, dU, Yb, dGb, Xb)
             if side_u:
-                _accumulate_rows(ctx.uparams, [dU[g * H:(g + 1) * H] for g in range(G)])
+                _accumulate_gate_rows(cfg.uparams, dU, G, H)
 
         # (the bottom layer has no dX GEMM and nothing below it to hide behind: its dU starts at once, next to its own
         # BatchNorm backward, and only the short dW is left for the tail of the step)
         late = settings.side_late and bool(ctx.needs_input_grad[0])
         if side_u and not late:
-            side_launch(do_dU, (Y, S, Yb, dGb, Xb, dU), ctx.uparams)
+            side_launch(do_dU, (Y, S, Yb, dGb, Xb, dU), cfg.uparams)
         elif not side_u:
             do_dU()
         # BatchNorm backward (or plain sum of the two directions) straight from dGb -> bf16 projection gradient
@@ -2183,16 +2187,16 @@ class RecLayerPerfFn(torch.autograd.Function):
         part = _new(int(lib.pk_bn_partial_floats(TB, GH)), like=dY)
         sum_g = _new(GH, like=dY)
         sum_gx = _new(GH, like=dY) if use_bn else None
-        g1 = ctypes.c_void_p(dGb.data_ptr() + 2 * TB * Gp) if bidir else None
+        g1 = ctypes.c_void_p(dGb.data_ptr() + 2 * TB * Gp) if cfg.bidir else None
         acc_g = acc_b = None
-        if use_bn and ctx.affine is not None:  # decided in forward: d gamma / d beta go straight into the flat .grad
-            acc_g = adjacent_view([q.grad for q in ctx.affine[0]])
-            acc_b = adjacent_view([q.grad for q in ctx.affine[1]])
+        if use_bn and cfg.affine is not None:  # decided in forward: d gamma / d beta go straight into the flat .grad
+            acc_g = adjacent_view([q.grad for q in cfg.affine[0]])
+            acc_b = adjacent_view([q.grad for q in cfg.affine[1]])
             if acc_g is None or acc_b is None:
                 raise _lib.PkError("perf-mode recurrent layer: the BatchNorm gradients left the flat buffer between forward "
                                    "and backward (optim.FlatParams.zero_grad() re-aliases them)")
         rc = lib.pk_bn_bwd_bf16(_stream(), _p(dGb), g1, Gp, G, H, _p(P), GH, TB, _p(mean) if use_bn else None,
-                                _p(var) if use_bn else None, eps, _p(gamma) if use_bn else None, float(TB), _p(part),
+                                _p(var) if use_bn else None, cfg.eps, _p(gamma) if use_bn else None, float(TB), _p(part),
                                 _p(sum_g), _p(sum_gx), _p(dPb), dPb.shape[1], _p(acc_b), _p(acc_g))
         _lib.check(rc, "pk_bn_bwd_bf16")
         dgamma = dbeta = dbias = None
@@ -2207,7 +2211,7 @@ class RecLayerPerfFn(torch.autograd.Function):
 
         def do_dW():
             nonlocal dW
-            gview = adjacent_view([q.grad for q in ctx.wparams]) if side_w else None
+            gview = adjacent_view([q.grad for q in cfg.wparams]) if side_w else None
             sk = _splitk_bf(_tiles_bf(GH, Kx), TB)
             if gview is not None and xseg is None:  # straight into the flat gradient of the layer's gates (beta = 1)
                 gemm_bf16(GH, Kx, TB, dPb, dPb.shape[1], 0, xb, xb.shape[1], 0, gview, Kx, beta=1.0, splitk=sk)
@@ -2225,10 +2229,10 @@ class RecLayerPerfFn(torch.autograd.Function):
                 nseg, seglen, segpad = xseg
                 dW = torch.cat([dWp[:, s_ * segpad:s_ * segpad + seglen] for s_ in range(nseg)], 1)
             if side_w:
-                _accumulate_rows(ctx.wparams, [dW[g * H:(g + 1) * H] for g in range(G)])
+                _accumulate_gate_rows(cfg.wparams, dW, G, H)
 
         if side_w and not late:
-            side_launch(do_dW, (dPb, xb, dWp), ctx.wparams)
+            side_launch(do_dW, (dPb, xb, dWp), cfg.wparams)
         dx = None
         if ctx.needs_input_grad[0]:  # dx[m,d] = sum_n dP[m,n] W[n,d]: A k-contiguous, B = W (plain pitch) k-major
             Wb2 = Wb if xseg is None else cvt_bf16(Wcat)
@@ -2241,9 +2245,9 @@ class RecLayerPerfFn(torch.autograd.Function):
                 held = int(lib.pk_rec_plan_cus(ndir * B, H))
                 free = max(int(lib.pk_num_cu()) - held, 0) if held > 0 else 0
             if side_u:
-                side_launch(_sized_for(free, do_dU), (Y, S, Yb, dGb, Xb, dU), ctx.uparams)
+                side_launch(_sized_for(free, do_dU), (Y, S, Yb, dGb, Xb, dU), cfg.uparams)
             if side_w:
-                side_launch(_sized_for(free, do_dW), (dPb, xb, dWp), ctx.wparams)
+                side_launch(_sized_for(free, do_dW), (dPb, xb, dWp), cfg.wparams)
         if not side_w:
             do_dW()
         return dx, None, (None if side_w else dW), dbias, (None if side_u else dU), dgamma, dbeta, None, None, None, None, None

@@ -363,6 +363,20 @@ def drain_mask_prefetch():
     F_._RefRng.sync_back()
 
 
+def _gate_matrix(params, side, allow_view):
+    """The gates' weight matrices of one recurrent layer, stacked row-wise.  allow_view: as a detached view of the flat
+    parameter buffer when optim.FlatParams packed the gates back to back.  Otherwise side = True gives a copy of the
+    detached gates, side = False the concatenation with its autograd history, or the parameter itself for one gate.
+    _Recurrent.forward asks for W / U of the perf node with (False, side_w / side_u or autograd off) and detaches the
+    result itself when side_w / side_u; for W / U of the general node with (side_w / side_u, the same)."""
+    m = F_.adjacent_view([q.detach() for q in params]) if allow_view else None
+    if m is not None:
+        return m
+    if side:
+        return torch.cat([q.detach() for q in params], 0)
+    return torch.cat(params, 0) if len(params) > 1 else params[0]
+
+
 class _Recurrent(nn.Module):
     """Shared body of LSTM / GRU / liGRU / minimalGRU / RNN (neural_networks.py:300-655, 997-1461)."""
 
@@ -530,12 +544,14 @@ class _Recurrent(nn.Module):
             masks = [m.to(x.device).float().contiguous() if m is not None else None for m in masks]
         batch = x.shape[1]
         xb = xseg = None  # perf mode: bf16 copy of the running activation, handed from layer to layer
-        for i in range(self._n_lay):
+        routes = [F_.rec_route(self.KIND, self._lay[i], bool(self._use_ln[i]), bool(self._use_bn[i]), self.training)
+                  for i in range(self._n_lay)]
+        for i, route in enumerate(routes):
             mask_i, scalar_i = (masks[i], scalars[i]) if masks is not None else self._drop_mask(i, batch, x.device)
             H = self._lay[i]
             Ws = [getattr(self, w)[i] for (w, _, _) in self._gates]
             Us = [getattr(self, u)[i] for (_, u, _) in self._gates]
-            Wcat = Ucat = None  # (concatenated below; on the perf path possibly as views of the flat parameter buffer)
+            wps, ups = [m.weight for m in Ws], [m.weight for m in Us]
             bcat = None
             if Ws[0].bias is not None:
                 bcat = torch.cat([m.bias for m in Ws], 0) if len(Ws) > 1 else Ws[0].bias
@@ -545,8 +561,7 @@ class _Recurrent(nn.Module):
             affine = edge_t = None
             if use_bn:
                 gps, bps = [b.weight for b in bns], [b.bias for b in bns]
-                if (self.training and F_.direct_affine_ok(gps + bps)
-                        and F_.perf_path_ok(self.KIND, H, bool(self._use_ln[i]), use_bn, self.training)):
+                if self.training and F_.direct_affine_ok(gps + bps) and route.perf:
                     # the engine's own training step: scales / shifts as views of the flat buffer (no concatenation
                     # launches), their gradients added to the flat .grad by the BatchNorm backward itself
                     gamma, beta = F_.adjacent_view([q.detach() for q in gps]), F_.adjacent_view([q.detach() for q in bps])
@@ -563,66 +578,41 @@ class _Recurrent(nn.Module):
                 # what torch's BatchNorm1d raises for the reference in the same situation (one row, training mode)
                 raise ValueError("Expected more than 1 value per channel when training, got input size %s"
                                  % (tuple(x.shape),))
-            cfg = (self.KIND, self._act[i], H, bool(self.bidir), use_bn, self.training, 1e-5, 0.05, scalar_i)
-            if F_.perf_path_ok(self.KIND, H, bool(self._use_ln[i]), use_bn, self.training):
-                wps, ups = [m.weight for m in Ws], [m.weight for m in Us]
-                # weight gradients that go to the flat .grad buffer from the side stream do not pass through autograd:
-                # the concatenated weights are handed over detached (otherwise cat's backward materialises a zero
-                # gradient per gate and adds it to .grad on the main stream - launches, and a write that would race
-                # a data-parallel bucket already being reduced)
-                # (some other input must still carry the autograd edge that makes backward run at all: the BatchNorm
-                # affine or the bias - one of the two always exists, neural_networks.py:1052-1055 - or x itself)
-                edge = torch.is_grad_enabled() and (use_bn or bcat is not None or x.requires_grad)
-                side_w = edge and F_.side_targets_ok(wps)
-                side_u = edge and F_.side_targets_ok(ups)
-                # detached weights: the concatenation is a view when optim.FlatParams packed the gates back to back
-                if side_w or not torch.is_grad_enabled():
-                    Wcat = F_.adjacent_view([w.detach() for w in wps])
-                if side_u or not torch.is_grad_enabled():
-                    Ucat = F_.adjacent_view([u.detach() for u in ups])
-                if Wcat is None:
-                    Wcat = torch.cat(wps, 0) if len(wps) > 1 else wps[0]
-                if Ucat is None:
-                    Ucat = torch.cat(ups, 0) if len(ups) > 1 else ups[0]
+            # weight gradients that go to the flat .grad buffer from the side stream do not pass through autograd: the
+            # concatenated weights are handed over detached (otherwise cat's backward materialises a zero gradient per gate
+            # and adds it to .grad on the main stream - launches, and a write that would race a data-parallel bucket
+            # already being reduced).  Some other input must still carry the autograd edge that makes backward run at all:
+            # the BatchNorm affine or the bias - one of the two always exists, neural_networks.py:1052-1055 - or x itself
+            edge = torch.is_grad_enabled() and (use_bn or bcat is not None or x.requires_grad)
+            base = (self.KIND, self._act[i], H, bool(self.bidir), use_bn, self.training, 1e-5, 0.05, scalar_i)
+            if route.perf:
+                side_w, side_u = edge and F_.side_targets_ok(wps), edge and F_.side_targets_ok(ups)
+                view_ok = not torch.is_grad_enabled()
+                Wcat, Ucat = _gate_matrix(wps, False, side_w or view_ok), _gate_matrix(ups, False, side_u or view_ok)
                 # training-mode BatchNorm: the running statistics of every gate's module are updated by the launch that
                 # turns the batch statistics into scale / shift (pk_bn_finalize_gates)
-                # forward-only chunks: an inner layer's fp32 output is read by nobody (the next layer takes the bf16 copy)
-                keep_y = torch.is_grad_enabled() or i == self._n_lay - 1
                 stats_in_kernel = use_bn and self.training
                 bn_bufs = ([b.running_mean for b in bns], [b.running_var for b in bns],
                            [b.num_batches_tracked for b in bns]) if stats_in_kernel else None
+                # forward-only chunks: an inner layer's fp32 output is read by nobody (the next layer takes the bf16 copy)
+                cfg = F_.RecCfg(*base, xseg=xseg, wparams=wps, uparams=ups, side_w=side_w, side_u=side_u, bn_bufs=bn_bufs,
+                                affine=affine, keep_y=torch.is_grad_enabled() or i == self._n_lay - 1, route=route)
                 y, bmean, bvar, xb = F_.RecLayerPerfFn.apply(x, xb, Wcat.detach() if side_w else Wcat, bcat,
                                                            Ucat.detach() if side_u else Ucat, gamma, beta, rmean, rvar,
-                                                           mask_i, cfg + (xseg, wps, ups, side_w, side_u, bn_bufs, affine,
-                                                                          keep_y), edge_t)
+                                                           mask_i, cfg, edge_t)
                 xseg = (2 if self.bidir else 1, H, (H + 7) // 8 * 8)
                 if stats_in_kernel:
                     x = y
                     continue
             else:
-                wps, ups = [m.weight for m in Ws], [m.weight for m in Us]
-                # exact-fp32 mode with flat-bucket parameters (round 6): the weight-gradient GEMMs go to the side stream and add
-                # into the flat .grad, so the concatenated weights are handed over detached, as on the perf path above (some
-                # other input carries the autograd edge: the BatchNorm affine, the bias or x itself)
-                edge = (not F_.bf16_mode()) and torch.is_grad_enabled() and (use_bn or bcat is not None or x.requires_grad)
-                side_w = edge and F_.side_targets_any_ok(wps)
-                side_u = edge and F_.side_targets_any_ok(ups)
-                if side_w:
-                    Wcat = F_.adjacent_view([w.detach() for w in wps])
-                    if Wcat is None:
-                        Wcat = torch.cat([w.detach() for w in wps], 0)
-                else:
-                    Wcat = torch.cat(wps, 0) if len(wps) > 1 else wps[0]
-                if side_u:
-                    Ucat = F_.adjacent_view([u.detach() for u in ups])
-                    if Ucat is None:
-                        Ucat = torch.cat([u.detach() for u in ups], 0)
-                else:
-                    Ucat = torch.cat(ups, 0) if len(ups) > 1 else ups[0]
-                lng = self.ln[i].gamma if self._use_ln[i] else None
-                lnb = self.ln[i].beta if self._use_ln[i] else None
+                # exact-fp32 mode with flat-bucket parameters (round 6): the weight-gradient GEMMs go to the side stream too
+                edge = edge and not F_.bf16_mode()
+                side_w, side_u = edge and F_.side_targets_any_ok(wps), edge and F_.side_targets_any_ok(ups)
+                Wcat, Ucat = _gate_matrix(wps, side_w, side_w), _gate_matrix(ups, side_u, side_u)
+                lng, lnb = (self.ln[i].gamma, self.ln[i].beta) if self._use_ln[i] else (None, None)
                 y, bmean, bvar = F_.RecLayerFn.apply(x, Wcat, bcat, Ucat, gamma, beta, rmean, rvar, mask_i, lng, lnb,
-                                                     cfg + (wps, ups, side_w, side_u))
+                                                     F_.RecCfg(*base, wparams=wps, uparams=ups, side_w=side_w, side_u=side_u,
+                                                               route=route))
                 xb = xseg = None
             if use_bn and self.training:
                 n = x.shape[0] * x.shape[1] * (2 if self.bidir else 1)

@@ -53,7 +53,7 @@ def test_concatenated_head_gradient_with_other_contributors(second_use):
                                            ("minimalGRU", "minimalgru", "relu")])
 def test_forward_only_chunks_save_nothing_and_change_nothing(kind, pre, act):
     """Validation / forward chunks (core.py:644-671: module.eval(), torch.no_grad()): the perf-mode recurrences save nothing
-    for a backward pass and the inner layers of a stack write no fp32 output (functional.RecLayerPerfFn, cfg[16]) - the
+    for a backward pass and the inner layers of a stack write no fp32 output (functional.RecLayerPerfFn, RecCfg.keep_y) - the
     stack's output must be BIT-identical to the same eval-mode forward with autograd on, which takes the training kernels."""
     nn_amd = importlib.import_module("pytorch-kaldi_amd.nn")
     H, T, B, D = 550, 23, 37, 40
