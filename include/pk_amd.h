@@ -432,6 +432,20 @@ int pk_adam_step(void* stream, float* p, const float* g, float* exp_avg, float* 
 int pk_fused_step(void* stream, int kind, float* p, float* g, float* s0, float* s1, float* s2, int64_t n, float lr, float h0,
                   float h1, float h2, float weight_decay, int step, int zero_grad, const int64_t* segs, int nseg,
                   uint16_t* shadow);
+/* The forms of torch.optim.RMSprop / SGD that pk_fused_step leaves out, with the same preconditions (n and every pointer
+ * multiples of 4 elements / 16 bytes, step counts from 1) and the same two things done on the way out (zero_grad, segs / nseg /
+ * shadow).  kind 0 RMSprop - h0 alpha, h1 eps, h2 momentum (>= 0); s0 square_avg, s1 momentum_buffer (NULL iff h2 == 0), s2
+ * grad_avg (NULL unless PK_OPT_CENTERED): sq = alpha sq + (1 - alpha) g^2, avg = sqrt(sq [- ga^2]) + eps, buf = momentum buf +
+ * g / avg, p -= lr buf (momentum 0: p -= lr g / avg).  kind 1 SGD - h0 momentum, h1 dampening, s0 momentum_buffer (NULL iff
+ * h0 == 0), s1 = s2 = NULL: buf = g at step 1 (dampening not applied), momentum buf + (1 - dampening) g afterwards; the
+ * update is buf, or g + momentum buf with PK_OPT_NESTEROV, which needs momentum > 0 and dampening == 0 as in torch.  In
+ * both, g += weight_decay p comes first.  A flag of the other kind, a buffer the form needs but that is NULL, and Adam
+ * (kind 2) are refused. */
+#define PK_OPT_CENTERED 1u
+#define PK_OPT_NESTEROV 2u
+int pk_fused_step_ex(void* stream, int kind, float* p, float* g, float* s0, float* s1, float* s2, int64_t n, float lr, float h0,
+                     float h1, float h2, float weight_decay, unsigned flags, int step, int zero_grad, const int64_t* segs,
+                     int nseg, uint16_t* shadow);
 
 /* persistent-recurrence health: number of spin time-outs since the last reset
  * (host-mapped counter, readable without a device sync). */

@@ -2,6 +2,9 @@
 // torch.optim.RMSprop / SGD / Adam exactly as utils.optimizer_init configures them
 // (utils.py:2106-2164; momentum-free, non-centred RMSprop in every shipped cfg).
 // One pass over {param, grad, state}: RMSprop 16 B/param read + 8 B/param written.
+// The other forms torch accepts (RMSprop momentum / centered, SGD dampening / nesterov: pk_fused_step_ex) add 4 B read and
+// 4 B written per state buffer; the fullest, RMSprop with momentum and centered, reads 20 B/param (p, g, sq, ga, buf) and
+// writes 16 B/param (p, sq, ga, buf), 20 B with the gradient zeroed on the way out.
 #include "pk_common.h"
 
 namespace {
@@ -132,6 +135,85 @@ __global__ void fused_step_kernel(float* __restrict__ p, float* __restrict__ g, 
     }
 }
 
+// ---- the remaining forms torch.optim.RMSprop / SGD accept (pk_fused_step_ex), beside the kernel above so that its three
+// instantiations stay what they were.  Same quads, same two side jobs; the form is a template parameter:
+//   KIND 0, RMSprop: A = momentum > 0 (s1 = momentum buffer), B = centered (s2 = gradient average); s0 = square average;
+//                    h0 = alpha, h1 = eps, h2 = momentum
+//   KIND 1, SGD:     A = momentum != 0 (s0 = momentum buffer), B = nesterov; h0 = momentum, h1 = dampening;
+//                    first: the buffer starts as the gradient, dampening not applied (torch)
+// Every load of a quad is issued before the arithmetic that needs it.
+__device__ __forceinline__ void shadow_store_quad(const f32x4& pv, long i, const long* __restrict__ segs, int nseg,
+                                                  unsigned short* __restrict__ shadow) {
+    int lo = 0, hi = nseg;  // the segment that holds element i: the last one that starts at or before it
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (segs[5 * mid] <= i) lo = mid;
+        else hi = mid;
+    }
+    const long off = segs[5 * lo], rows = segs[5 * lo + 1], cols = segs[5 * lo + 2], pitch = segs[5 * lo + 3], soff = segs[5 * lo + 4];
+    const long rel = i - off;
+    if (rel >= 0 && rel < rows * cols) {  // (columns are a multiple of 4: the four elements share a row)
+        const long row = rel / cols, col = rel - row * cols;
+        uint2 pk;
+        pk.x = pk_pack_bf2(pv[0], pv[1]);
+        pk.y = pk_pack_bf2(pv[2], pv[3]);
+        *reinterpret_cast<uint2*>(shadow + soff + row * pitch + col) = pk;
+    }
+}
+
+template <int KIND, bool A, bool B>
+__global__ void fused_step_ex_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict__ s0, float* __restrict__ s1,
+                                     float* __restrict__ s2, long n, float lr, float h0, float h1, float h2, float wd, int first,
+                                     int zero_grad, const long* __restrict__ segs, int nseg, unsigned short* __restrict__ shadow) {
+    constexpr bool L0 = KIND == 0 || A, L1 = KIND == 0 && A, L2 = KIND == 0 && B;  // which state buffers the form touches
+    for (long i = 4 * (blockIdx.x * (long)blockDim.x + threadIdx.x); i < n; i += 4 * (long)gridDim.x * blockDim.x) {
+        f32x4 gv = *reinterpret_cast<const f32x4*>(g + i);
+        f32x4 pv = *reinterpret_cast<const f32x4*>(p + i);
+        f32x4 a = {0.f, 0.f, 0.f, 0.f}, b = a, c = a;
+        if (L0) a = *reinterpret_cast<const f32x4*>(s0 + i);
+        if (L1) b = *reinterpret_cast<const f32x4*>(s1 + i);
+        if (L2) c = *reinterpret_cast<const f32x4*>(s2 + i);
+        if (wd != 0.f) {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) gv[e] += wd * pv[e];
+        }
+        if (KIND == 0) {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                a[e] = h0 * a[e] + (1.f - h0) * gv[e] * gv[e];
+                float avg;
+                if (B) {
+                    c[e] = h0 * c[e] + (1.f - h0) * gv[e];
+                    avg = sqrtf(a[e] - c[e] * c[e]) + h1;
+                } else {
+                    avg = sqrtf(a[e]) + h1;
+                }
+                if (A) {
+                    b[e] = h2 * b[e] + gv[e] / avg;
+                    pv[e] = pv[e] - lr * b[e];
+                } else {
+                    pv[e] = pv[e] - lr * gv[e] / avg;
+                }
+            }
+        } else {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                if (A) {
+                    a[e] = first ? gv[e] : h0 * a[e] + (1.f - h1) * gv[e];
+                    gv[e] = B ? gv[e] + h0 * a[e] : a[e];
+                }
+                pv[e] = pv[e] - lr * gv[e];
+            }
+        }
+        if (L0) *reinterpret_cast<f32x4*>(s0 + i) = a;
+        if (L1) *reinterpret_cast<f32x4*>(s1 + i) = b;
+        if (L2) *reinterpret_cast<f32x4*>(s2 + i) = c;
+        *reinterpret_cast<f32x4*>(p + i) = pv;
+        if (zero_grad) *reinterpret_cast<f32x4*>(g + i) = f32x4{0.f, 0.f, 0.f, 0.f};
+        if (nseg > 0) shadow_store_quad(pv, i, segs, nseg, shadow);
+    }
+}
+
 inline int blocks_for(long n) {
     long b = (n + 255) / 256;
     if (b > 4096) b = 4096;
@@ -195,6 +277,52 @@ extern "C" int pk_fused_step(void* stream, int kind, float* p, float* g, float* 
     if (kind == 0) hipLaunchKernelGGL(fused_step_kernel<0>, grid, block, 0, st, p, g, s0, s1, s2, (long)n, lr, h0, h1, h2, weight_decay, bc1, bc2s, 0, zero_grad, sg, nseg, (unsigned short*)shadow);
     else if (kind == 1) hipLaunchKernelGGL(fused_step_kernel<1>, grid, block, 0, st, p, g, s0, s1, s2, (long)n, lr, h0, h1, h2, weight_decay, bc1, bc2s, step == 1 ? 1 : 0, zero_grad, sg, nseg, (unsigned short*)shadow);
     else hipLaunchKernelGGL(fused_step_kernel<2>, grid, block, 0, st, p, g, s0, s1, s2, (long)n, lr, h0, h1, h2, weight_decay, bc1, bc2s, 0, zero_grad, sg, nseg, (unsigned short*)shadow);
+    PK_LAUNCH_CHECK();
+    return 0;
+}
+
+// The forms pk_fused_step does not cover, same preconditions.  kind 0 = RMSprop: h0 = alpha, h1 = eps, h2 = momentum;
+// s0 = square average, s1 = momentum buffer (h2 > 0), s2 = gradient average (PK_OPT_CENTERED).  kind 1 = SGD: h0 = momentum,
+// h1 = dampening, PK_OPT_NESTEROV; s0 = momentum buffer (h0 != 0); step == 1 is torch's first step (buffer = gradient).
+extern "C" int pk_fused_step_ex(void* stream, int kind, float* p, float* g, float* s0, float* s1, float* s2, int64_t n, float lr,
+                                float h0, float h1, float h2, float weight_decay, unsigned flags, int step, int zero_grad,
+                                const int64_t* segs, int nseg, uint16_t* shadow) {
+    if (n == 0) return 0;
+    PK_REQUIRE(kind >= 0 && kind <= 1 && step >= 1, "pk_fused_step_ex: kind 0 (RMSprop) or 1 (SGD), step counts from 1");
+    PK_REQUIRE((flags & ~(unsigned)(PK_OPT_CENTERED | PK_OPT_NESTEROV)) == 0, "pk_fused_step_ex: unknown flag");
+    PK_REQUIRE((n & 3) == 0 && (((uintptr_t)p | (uintptr_t)g | (uintptr_t)s0 | (uintptr_t)s1 | (uintptr_t)s2) & 15) == 0,
+               "pk_fused_step_ex: n and the buffers must be multiples of 4 elements / 16-byte aligned");
+    PK_REQUIRE(nseg == 0 || (segs != nullptr && shadow != nullptr && ((uintptr_t)shadow & 7) == 0), "pk_fused_step_ex: null segment table / copy");
+    const bool centered = (flags & PK_OPT_CENTERED) != 0, nesterov = (flags & PK_OPT_NESTEROV) != 0;
+    const dim3 grid(blocks_for(n / 4)), block(256);
+    hipStream_t st = pk_stream(stream);
+    const long* sg = reinterpret_cast<const long*>(segs);
+    unsigned short* sh = reinterpret_cast<unsigned short*>(shadow);
+#define PK_LAUNCH_EX(K, A, B, FIRST)                                                                                         \
+    hipLaunchKernelGGL((fused_step_ex_kernel<K, A, B>), grid, block, 0, st, p, g, s0, s1, s2, (long)n, lr, h0, h1, h2, \
+                       weight_decay, FIRST, zero_grad, sg, nseg, sh)
+    if (kind == 0) {
+        PK_REQUIRE(!nesterov, "pk_fused_step_ex: nesterov is an SGD flag");
+        PK_REQUIRE(h2 >= 0.f, "pk_fused_step_ex: RMSprop momentum must not be negative");
+        const bool mom = h2 > 0.f;
+        PK_REQUIRE(s0 != nullptr, "pk_fused_step_ex: RMSprop needs its square average");
+        PK_REQUIRE(!mom || s1 != nullptr, "pk_fused_step_ex: RMSprop momentum needs a buffer");
+        PK_REQUIRE(!centered || s2 != nullptr, "pk_fused_step_ex: centered RMSprop needs its gradient average");
+        if (mom && centered) PK_LAUNCH_EX(0, true, true, 0);
+        else if (mom) PK_LAUNCH_EX(0, true, false, 0);
+        else if (centered) PK_LAUNCH_EX(0, false, true, 0);
+        else PK_LAUNCH_EX(0, false, false, 0);
+    } else {
+        PK_REQUIRE(!centered, "pk_fused_step_ex: centered is an RMSprop flag");
+        PK_REQUIRE(!nesterov || (h0 > 0.f && h1 == 0.f), "pk_fused_step_ex: Nesterov momentum requires a momentum and zero dampening");
+        const bool mom = h0 != 0.f;
+        PK_REQUIRE(!mom || s0 != nullptr, "pk_fused_step_ex: momentum needs a buffer");
+        const int first = step == 1 ? 1 : 0;
+        if (mom && nesterov) PK_LAUNCH_EX(1, true, true, first);
+        else if (mom) PK_LAUNCH_EX(1, true, false, first);
+        else PK_LAUNCH_EX(1, false, false, first);
+    }
+#undef PK_LAUNCH_EX
     PK_LAUNCH_CHECK();
     return 0;
 }

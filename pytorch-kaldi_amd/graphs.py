@@ -21,8 +21,9 @@ class GraphedStep:
 
     The caller runs a few eager steps first (lazy one-time initialisation - kernel attributes, allocator pools -
     must not happen inside the capture).  Fused optimizers whose step count is a kernel ARGUMENT (Adam's bias
-    correction) cannot be replayed: pass them in ``optimizers`` and capture refuses them; for the others the python
-    side step counters are advanced per replay so that checkpoints keep counting."""
+    correction) cannot be replayed: pass them in ``optimizers`` and capture refuses them; for the others (RMSprop and
+    SGD in every form; SGD's first-step flag is baked as 0, the warm-up steps having been taken) the python side step
+    counters are advanced per replay so that checkpoints keep counting."""
 
     def __init__(self, step_fn, optimizers=()):
         self.step_fn = step_fn

@@ -8,7 +8,15 @@ and (ii) the data-parallel gradient exchange (dp.py) all-reduces slices of that
 same buffer with no packing copies.
 
 Semantics follow ``torch.optim.RMSprop`` / ``SGD`` / ``Adam`` exactly as
-``utils.optimizer_init`` configures them (utils.py:2106-2164).  Parameters the
+``utils.optimizer_init`` configures them (utils.py:2106-2164), in every form the
+recipe fields reach: ``opt_momentum`` and ``opt_centered`` for RMSprop,
+``opt_momentum``, ``opt_dampening`` and ``opt_nesterov`` for SGD.  The plain forms
+(momentum-free, non-centred RMSprop; SGD without dampening or Nesterov; Adam) run
+``pk_fused_step``, the others ``pk_fused_step_ex`` - the same single pass with one
+more flat state buffer per option (``momentum_buffer``, ``grad_avg``; the fullest,
+RMSprop with momentum and centered, reads 20 B and writes 16 to 20 B per
+parameter).  What torch refuses (Nesterov without momentum or with dampening) is
+refused here.  Parameters the
 reference leaves without a gradient (its unused ``ln``/``bn`` sub-modules,
 SURVEY.md 7.2; a module lists them in ``pk_unused_parameters()``) are laid out
 BEHIND the active ones: the fused step covers the active range only, so they are
@@ -157,36 +165,47 @@ class FusedOptimizer:
     ``param_groups`` with the torch hyper-parameter names), so the ``optimizer_par`` of a ``.pkl`` checkpoint
     written by the reference loads here and vice versa (core.py:531-532, 708-722)."""
 
-    _STATE_KEYS = {"rmsprop": ("square_avg",), "sgd": ("momentum_buffer",),
+    # every flat state buffer a kind can have, under torch's key names; _state_keys() picks what the form at hand needs
+    _STATE_KEYS = {"rmsprop": ("square_avg", "momentum_buffer", "grad_avg"), "sgd": ("momentum_buffer",),
                    "adam": ("exp_avg", "exp_avg_sq", "max_exp_avg_sq")}
 
     def __init__(self, flat, kind, lr, alpha=0.99, eps=1e-8, momentum=0.0, weight_decay=0.0, centered=False,
                  dampening=0.0, nesterov=False, betas=(0.9, 0.999), amsgrad=False):
         if kind not in ("rmsprop", "sgd", "adam"):
             raise _lib.PkError("fused optimizer covers rmsprop, sgd and adam (got %s)" % kind)
-        if kind == "rmsprop" and (momentum != 0.0 or centered):
-            raise _lib.PkError("fused RMSprop is the momentum-free, non-centred form every shipped recipe uses")
-        if kind == "sgd" and (dampening != 0.0 or nesterov):
-            raise _lib.PkError("fused SGD does not implement dampening / nesterov")
         self.flat, self.kind, self.lr = flat, kind, lr
         self.alpha, self.eps, self.momentum, self.weight_decay = alpha, eps, momentum, weight_decay
+        self.centered, self.dampening, self.nesterov = bool(centered), dampening, bool(nesterov)
         self.betas, self.amsgrad = tuple(betas), bool(amsgrad)
-        z = lambda: torch.zeros_like(flat.flat)
-        self.bufs = {}
-        if kind == "rmsprop":
-            self.bufs["square_avg"] = z()
-        elif kind == "sgd" and momentum != 0.0:
-            self.bufs["momentum_buffer"] = z()
-        elif kind == "adam":
-            self.bufs["exp_avg"], self.bufs["exp_avg_sq"] = z(), z()
-            if self.amsgrad:
-                self.bufs["max_exp_avg_sq"] = z()
+        self._check_form()
+        self.bufs = {k: torch.zeros_like(flat.flat) for k in self._state_keys()}
         self.steps = 0
         self.param_groups = [{"lr": lr}]  # run_nn overrides the LR through param_groups (core.py:533-535)
         # True: step() leaves the flat gradient zeroed (and the following zero_grad() skips its fill launch).  For loops
         # that call zero_grad() in front of every backward pass anyway - core.run_nn_dp, bench.py - and never read .grad
         # behind step(); off by default (torch.optim leaves .grad alone).  PK_EXPERIMENT opt_zero_in_step=0 turns it off everywhere.
         self.zero_in_step = False
+
+    def _check_form(self):
+        """What torch.optim refuses for these hyper-parameters (the kernels have no meaning for them either)."""
+        if self.kind != "adam" and self.momentum < 0.0:
+            raise _lib.PkError("Invalid momentum value: %s" % self.momentum)
+        if self.kind == "sgd" and self.nesterov and (self.momentum <= 0.0 or self.dampening != 0.0):
+            raise _lib.PkError("Nesterov momentum requires a momentum and zero dampening")
+
+    def _state_keys(self):
+        """The flat state buffers the form at hand keeps, by need (torch allocates the same ones per parameter)."""
+        if self.kind == "rmsprop":
+            return ("square_avg",) + (("momentum_buffer",) if self.momentum > 0.0 else ()) + (("grad_avg",) if self.centered else ())
+        if self.kind == "sgd":
+            return ("momentum_buffer",) if self.momentum != 0.0 else ()
+        return ("exp_avg", "exp_avg_sq") + (("max_exp_avg_sq",) if self.amsgrad else ())
+
+    def _extended(self):
+        """A form only pk_fused_step_ex has a kernel for (the plain ones keep the entries and kernels they always had)."""
+        if self.kind == "rmsprop":
+            return self.momentum > 0.0 or self.centered
+        return self.kind == "sgd" and (self.dampening != 0.0 or self.nesterov)
 
     @property
     def state(self):  # the (first) flat state buffer; kept for callers that only need "the" state
@@ -204,20 +223,30 @@ class FusedOptimizer:
         lr = float(self.param_groups[0]["lr"])
         f = self.flat
         ptr = lambda k: self.bufs[k].data_ptr() if k in self.bufs else None
-        if f.n_active % 4 == 0 and _lib.experiment("fused_step", "1") != "0":
+        ext = self._extended()
+        if ext and f.n_active % 4 != 0:
+            raise _lib.PkError("this optimizer form has a fused kernel only: the flat bucket must be a multiple of 4 elements")
+        if ext or (f.n_active % 4 == 0 and _lib.experiment("fused_step", "1") != "0"):
             # one launch that also zeroes the gradient (zero_in_step) and refreshes the bf16 copies of the weights
             if f._shadow_req and not torch.cuda.is_current_stream_capturing():
                 f.build_shadows()
             nseg = len(f._shadow_have)
             zero = bool(self.zero_in_step) and _lib.experiment("opt_zero_in_step", "1") != "0"
             kind = {"rmsprop": 0, "sgd": 1, "adam": 2}[self.kind]
-            h = {"rmsprop": (self.alpha, self.eps, 0.0), "sgd": (self.momentum, 0.0, 0.0),
-                 "adam": (self.betas[0], self.betas[1], self.eps)}[self.kind]
-            s0 = ptr("square_avg") if kind == 0 else ptr("momentum_buffer") if kind == 1 else ptr("exp_avg")
-            rc = lib.pk_fused_step(_stream(), kind, f.flat.data_ptr(), f.grad.data_ptr(), s0, ptr("exp_avg_sq"),
-                                   ptr("max_exp_avg_sq"), f.n_active, lr, h[0], h[1], h[2], self.weight_decay, self.steps + 1,
-                                   int(zero), f.shadow_segs.data_ptr() if nseg else None, nseg,
-                                   f.shadow.data_ptr() if nseg else None)
+            segs, shadow = (f.shadow_segs.data_ptr(), f.shadow.data_ptr()) if nseg else (None, None)
+            if ext:  # RMSprop with momentum / centered, SGD with dampening / nesterov: the same step, their own kernels
+                h = (self.alpha, self.eps, self.momentum) if kind == 0 else (self.momentum, self.dampening, 0.0)
+                s = (ptr("square_avg"), ptr("momentum_buffer"), ptr("grad_avg")) if kind == 0 else (ptr("momentum_buffer"), None, None)
+                flags = (1 if self.centered and kind == 0 else 0) | (2 if self.nesterov and kind == 1 else 0)
+                rc = lib.pk_fused_step_ex(_stream(), kind, f.flat.data_ptr(), f.grad.data_ptr(), s[0], s[1], s[2], f.n_active, lr,
+                                          h[0], h[1], h[2], self.weight_decay, flags, self.steps + 1, int(zero), segs, nseg, shadow)
+            else:
+                h = {"rmsprop": (self.alpha, self.eps, 0.0), "sgd": (self.momentum, 0.0, 0.0),
+                     "adam": (self.betas[0], self.betas[1], self.eps)}[self.kind]
+                s0 = ptr("square_avg") if kind == 0 else ptr("momentum_buffer") if kind == 1 else ptr("exp_avg")
+                rc = lib.pk_fused_step(_stream(), kind, f.flat.data_ptr(), f.grad.data_ptr(), s0, ptr("exp_avg_sq"),
+                                       ptr("max_exp_avg_sq"), f.n_active, lr, h[0], h[1], h[2], self.weight_decay,
+                                       self.steps + 1, int(zero), segs, nseg, shadow)
             _lib.check(rc, "fused optimizer step")
             f._clean = zero
             self.steps += 1
@@ -242,9 +271,11 @@ class FusedOptimizer:
         ps = self.flat.params
         lr = float(self.param_groups[0]["lr"])
         if self.kind == "rmsprop":
-            return optim.RMSprop(ps, lr=lr, alpha=self.alpha, eps=self.eps, weight_decay=self.weight_decay)
+            return optim.RMSprop(ps, lr=lr, alpha=self.alpha, eps=self.eps, weight_decay=self.weight_decay,
+                                 momentum=self.momentum, centered=self.centered)
         if self.kind == "sgd":
-            return optim.SGD(ps, lr=lr, momentum=self.momentum, weight_decay=self.weight_decay)
+            return optim.SGD(ps, lr=lr, momentum=self.momentum, weight_decay=self.weight_decay, dampening=self.dampening,
+                             nesterov=self.nesterov)
         return optim.Adam(ps, lr=lr, betas=self.betas, eps=self.eps, weight_decay=self.weight_decay, amsgrad=self.amsgrad)
 
     def state_dict(self):
@@ -271,13 +302,18 @@ class FusedOptimizer:
         self.weight_decay = float(g.get("weight_decay", self.weight_decay))
         if self.kind == "rmsprop":
             self.alpha, self.eps = float(g.get("alpha", self.alpha)), float(g.get("eps", self.eps))
+            self.momentum, self.centered = float(g.get("momentum", self.momentum)), bool(g.get("centered", self.centered))
         elif self.kind == "sgd":
-            self.momentum = float(g.get("momentum", self.momentum))
+            self.momentum, self.dampening = float(g.get("momentum", self.momentum)), float(g.get("dampening", self.dampening))
+            self.nesterov = bool(g.get("nesterov", self.nesterov))
         else:
             self.betas, self.eps = tuple(g.get("betas", self.betas)), float(g.get("eps", self.eps))
+        self._check_form()
         steps = 0
-        for b in self.bufs.values():
-            b.zero_()
+        # the buffers follow the loaded form (torch takes the loaded group as it is): keep what it still needs, allocate
+        # what it lacks, release the rest; zeros - torch's initial value of every buffer - wherever an entry has no such key
+        old = self.bufs
+        self.bufs = {k: old[k].zero_() if k in old else torch.zeros_like(self.flat.flat) for k in self._state_keys()}
         for i, ent in sd["state"].items():  # parameters torch never stepped (grad None) have no entry: zeros
             i = int(i)
             p, o = self.flat.params[i], self.flat.offsets[i]
