@@ -892,6 +892,32 @@ def oracle_extra_cases():
            "cnn_use_laynorm": "True,False", "cnn_use_batchnorm": "False,True",
            "cnn_act": "leaky_relu,relu", "cnn_drop": "0.0,0.0"}
     module_case("ora_cnn_lninp_eval", "CNN", cnn, 90, (5, 90), 950, x_scale=0.5, to_do="valid", training=False)
+    mixed_stack_cases()
+
+
+def mixed_stack_opts(pre, lay, act, ln, bn, drop, **kw):
+    """rec_opts takes one value for all layers: the per-layer keys are overridden on the dict it returns."""
+    o = rec_opts(pre, lay, act[0], **kw)
+    for key, vals in (("_act", act), ("_use_laynorm", ln), ("_use_batchnorm", bn), ("_drop", drop)):
+        assert len(vals) == len(lay)
+        o[pre + key] = ",".join(map(str, vals))
+    return o
+
+
+def mixed_stack_cases():
+    """Stacks whose layers differ in width, activation, normalisation and dropout rate (the reference reads all of
+    them per layer): every other fixture repeats one value per layer.  F / T below: False / True."""
+    F, T = False, True
+    module_case("ora_ligru_mixed_stack", "liGRU", mixed_stack_opts(
+        "ligru", [20, 12, 16], ["relu", "tanh", "leaky_relu"], [F, T, F], [T, F, F], [0.2, 0.0, 0.1]), 7, (8, 3, 7), 960)
+    module_case("ora_lstm_mixed_stack", "LSTM", mixed_stack_opts(
+        "lstm", [14, 17, 10], ["tanh", "tanh", "sigmoid"], [T, F, F], [F, T, F], [0.1, 0.3, 0.0]), 6, (7, 4, 6), 965)
+    module_case("ora_gru_mixed_stack", "GRU", mixed_stack_opts(
+        "gru", [12, 11, 13], ["tanh", "relu", "tanh"], [F, F, T], [T, F, F], [0.2, 0.2, 0.1], bidir=False), 5, (9, 4, 5), 970)
+    module_case("ora_mingru_mixed_stack_eval", "minimalGRU", mixed_stack_opts(
+        "minimalgru", [10, 15], ["relu", "tanh"], [F, T], [T, F], [0.2, 0.1]), 4, (6, 3, 4), 975, to_do="valid", training=False)
+    module_case("ora_rnn_mixed_stack", "RNN", mixed_stack_opts(
+        "rnn", [13, 9, 11], ["relu", "tanh", "elu"], [F, T, F], [T, F, T], [0.0, 0.2, 0.1]), 5, (8, 3, 5), 980)
 
 
 def model_lang_case(name, seed):
@@ -1095,6 +1121,9 @@ def main():
         return
     if os.environ.get("PK_GOLDEN_ONLY") == "oracle_extra":
         oracle_extra_cases()
+        return
+    if os.environ.get("PK_GOLDEN_ONLY") == "mixed_stacks":
+        mixed_stack_cases()
         return
     # --- recurrent family -----------------------------------------------------
     module_case("ligru_bidir_bn", "liGRU", rec_opts("ligru", [24, 16], "relu"), 7, (9, 3, 7), 100)

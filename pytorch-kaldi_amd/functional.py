@@ -1604,8 +1604,10 @@ def choose_rec_algo(cell, H, use_ln):
     gen4 = (not bf16_mode() and cell in ("LSTM", "GRU", "minimalGRU") and _lib.experiment("rec_f32_gen4", "1")[:1] != "0"
             and (not use_ln or ln_persistent_ok(cell, H)))
     ok = cell in ("liGRU", "RNN", "LSTM") and H <= 576 and (not use_ln or ln_persistent_ok(cell, H))
-    if cell in ("GRU", "minimalGRU"):  # bf16 two-phase kernels on this (general) path: the layers that normalise h_t
-        ok = H <= 576 and ((use_ln and ln_persistent_ok(cell, H)) or gen4)
+    if cell in ("GRU", "minimalGRU"):
+        # bf16 two-phase kernels on this (general) path: the layers that normalise h_t, and the layers the perf node hands
+        # back (frozen BatchNorm statistics with autograd on) - the same kernel as the no_grad forward of the same layer
+        ok = H <= 576 and ((use_ln and ln_persistent_ok(cell, H)) or gen4 or (bf16_mode() and not use_ln))
     # the first-generation exact-fp32 kernels exchange pairs of fp32 values: LSTM without generation 4, liGRU / RNN when
     # PK_EXPERIMENT rec_f32_gen=1 keeps them (the library reads the same switch, pk_rec_persist.hip::use_gen2_f32)
     if not bf16_mode() and not gen4 and (cell == "LSTM" or _lib.experiment("rec_f32_gen", "")[:1] == "1"):
@@ -1650,7 +1652,17 @@ def rec_route(cell, H, use_ln, use_bn, training):
     algo = choose_rec_algo(cell, H, use_ln)
     if not bf16_mode() or algo != REC_PERSISTENT:
         return RecRoute(False, algo, "generic")
-    return RecRoute(False, algo, ("2p_bf16_ln" if two_phase else "bf16_ln") if use_ln else "bf16")
+    if use_ln:
+        return RecRoute(False, algo, "2p_bf16_ln" if two_phase else "bf16_ln")
+    return RecRoute(False, algo, "2p_bf16" if two_phase else "bf16")
+
+
+def rec_keep_y(routes, i, grad_enabled):
+    """Whether layer i of a stack (routes: its layers' RecRoute, bottom first) writes its fp32 output.  A forward-only
+    chunk skips it for an inner perf layer whose successor is a perf layer too - that one reads the bf16 copy Yb.  The
+    general node (a layer with per-step LayerNorm, H > 576, ...) takes the fp32 tensor as its input and always writes its
+    own, and so does whoever called the stack; with autograd on the output is saved for backward."""
+    return bool(grad_enabled or i == len(routes) - 1 or not routes[i].perf or not routes[i + 1].perf)
 
 
 class RecCfg(NamedTuple):
@@ -2121,8 +2133,8 @@ class RecLayerPerfFn(torch.autograd.Function):
             mean, var, pscale, pshift = _proj_scale_shift(cfg, P, mean, var, gamma, beta, running_mean, running_var, bcat)
         # A validation / forward chunk (torch.no_grad, core.py:644-671: nothing here needs a gradient) saves nothing for a
         # backward pass: no S (563 MB per Li-GRU layer at the BASELINE shape), and an INNER layer of a stack does not write
-        # its fp32 output either - the next layer reads the bf16 copy Yb (cfg.keep_y, set by nn._Recurrent.forward; the
-        # tensor returned in its place carries the shape only).
+        # its fp32 output either when the next layer is a perf layer too and reads the bf16 copy Yb (cfg.keep_y = rec_keep_y,
+        # set by nn._Recurrent.forward; the tensor returned in its place carries the shape only).
         infer = not any(ctx.needs_input_grad) and _Kinks.queue is None and _lib.experiment("fwd_nosave", "1") != "0"
         Y = _new(T, B, ndir * H, like=Wcat)
         S = None if infer else _new(ndir, TB, geom.NS * H, like=Wcat)

@@ -594,9 +594,10 @@ class _Recurrent(nn.Module):
                 stats_in_kernel = use_bn and self.training
                 bn_bufs = ([b.running_mean for b in bns], [b.running_var for b in bns],
                            [b.num_batches_tracked for b in bns]) if stats_in_kernel else None
-                # forward-only chunks: an inner layer's fp32 output is read by nobody (the next layer takes the bf16 copy)
+                # forward-only chunks: an inner layer's fp32 output is read by nobody when the next layer is a perf node too
+                # (it takes the bf16 copy; the general node reads the fp32 tensor): functional.rec_keep_y
                 cfg = F_.RecCfg(*base, xseg=xseg, wparams=wps, uparams=ups, side_w=side_w, side_u=side_u, bn_bufs=bn_bufs,
-                                affine=affine, keep_y=torch.is_grad_enabled() or i == self._n_lay - 1, route=route)
+                                affine=affine, keep_y=F_.rec_keep_y(routes, i, torch.is_grad_enabled()), route=route)
                 y, bmean, bvar, xb = F_.RecLayerPerfFn.apply(x, xb, Wcat.detach() if side_w else Wcat, bcat,
                                                            Ucat.detach() if side_u else Ucat, gamma, beta, rmean, rvar,
                                                            mask_i, cfg, edge_t)
