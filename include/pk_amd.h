@@ -209,7 +209,11 @@ int pk_ln_last_act_drop_bwd(void* stream, const float* dy, const float* z, const
                             float* pg);
 
 /* ---- LayerNorm: neural_networks.py:23-33 (unbiased std, eps added to std).
- * Rows of length F; saves mean and 1/(std+eps) per row for backward. */
+ * Rows of length F; saves mean and 1/(std+eps) per row for backward.
+ * A row of variance 0 (std == 0, e.g. an all-zero padded frame) has the gradient rinv * (g - mean(g)), as torch's
+ * std() backward defines it (0 where std == 0): this holds for every LayerNorm backward of the library (pk_layernorm_bwd,
+ * pk_ln_last_act_drop_bwd, the per-step LayerNorm of pk_rec_bwd and of the persistent recurrences).  Rows with
+ * |mean| > 64 std are normalised with the rounding error of the mean taken out of the deviations (pk_layernorm_*). */
 int pk_layernorm_fwd(void* stream, const float* x, int64_t rows, int64_t F, const float* gamma, const float* beta,
                      float eps, float* y, float* mean, float* rinv);
 /* dx; dgamma/dbeta are produced as per-row-block partials reduced by pk_colsum
@@ -218,7 +222,9 @@ int pk_layernorm_fwd(void* stream, const float* x, int64_t rows, int64_t F, cons
 int pk_layernorm_bwd(void* stream, const float* dy, const float* x, int64_t rows, int64_t F, const float* gamma,
                      const float* mean, const float* rinv, float eps, float* dx, float* dgx);
 
-/* ---- LogSoftmax(dim=1): neural_networks.py:53-54 ('softmax' activation) */
+/* ---- LogSoftmax(dim=1): neural_networks.py:53-54 ('softmax' activation).  Rows whose maximum m lies beyond +-32 are
+ * written as (x - m) - log(sum exp(x - m)), so that a common level of the logits costs no accuracy; the others as
+ * x - (m + log(sum ...)) (the same value up to one rounding). */
 int pk_logsoftmax_fwd(void* stream, const float* x, int64_t rows, int64_t N, float* y);
 int pk_logsoftmax_bwd(void* stream, const float* dy, const float* y, int64_t rows, int64_t N, float* dx);
 /* the same backward writing dx at a pitch of lddx floats (N rounded up to a multiple of 4: 16-byte aligned rows for the

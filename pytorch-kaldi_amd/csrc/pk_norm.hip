@@ -613,6 +613,7 @@ __device__ __forceinline__ float block_max(float v, float* sh) {
 }
 
 // ---- LayerNorm of the reference: gamma*(x-mean)/(std_unbiased+eps)+beta ----------
+constexpr float LN_FAR = 64.f;  // |mean| / (std + eps) beyond which layernorm_fwd / _bwd correct the rounding of the mean
 __global__ __launch_bounds__(256) void layernorm_fwd_kernel(const float* __restrict__ x, long rows, long F,
                                                              const float* __restrict__ gamma,
                                                              const float* __restrict__ beta, float eps,
@@ -629,10 +630,22 @@ __global__ __launch_bounds__(256) void layernorm_fwd_kernel(const float* __restr
             const float d = xr[f] - mu;
             q += d * d;
         }
-        const float var = block_sum(q, sh) / (float)(F - 1);
-        const float rinv = 1.0f / (sqrtf(var) + eps);
+        float var = block_sum(q, sh) / (float)(F - 1);
+        float rinv = 1.0f / (sqrtf(var) + eps);
+        // A row far from zero (|mean| > LN_FAR std): mu is rounded to an ulp of the LEVEL, eps * |mean| / std of the spread
+        // (1e3 + N(0,1): 5e-5 of y).  x - mu is exact there, so the mean of the deviations IS that rounding error: take it
+        // out (the corrected two-pass form).  A select: every other row keeps dc = 0 and its bits.
+        float dc = 0.f;
+        if (fabsf(mu) * rinv > LN_FAR) {
+            float sd = 0.f;
+            for (long f = threadIdx.x; f < F; f += blockDim.x) sd += xr[f] - mu;
+            sd = block_sum(sd, sh);
+            dc = sd / (float)F;
+            var = fmaxf(var - sd * dc / (float)(F - 1), 0.f);
+            rinv = 1.0f / (sqrtf(var) + eps);
+        }
         for (long f = threadIdx.x; f < F; f += blockDim.x)
-            y[r * F + f] = gamma[f] * ((xr[f] - mu) * rinv) + beta[f];
+            y[r * F + f] = gamma[f] * (((xr[f] - mu) - dc) * rinv) + beta[f];
         if (threadIdx.x == 0) {
             mean_o[r] = mu;
             rinv_o[r] = rinv;
@@ -650,18 +663,27 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const float* __restr
     for (long r = blockIdx.x; r < rows; r += gridDim.x) {
         const float mu = mean[r], rinv = rinv_i[r];
         const float stdv = 1.0f / rinv - eps;
-        float sg = 0.f, sgd = 0.f;
+        const bool far = fabsf(mu) * rinv > LN_FAR;  // (see layernorm_fwd_kernel: d = (x - mu) - dc on such a row)
+        float sg = 0.f, sgd = 0.f, sd = 0.f;
         for (long f = threadIdx.x; f < F; f += blockDim.x) {
             const float g = dy[r * F + f] * gamma[f];
             sg += g;
             sgd += g * (x[r * F + f] - mu);
+            if (far) sd += x[r * F + f] - mu;
         }
         sg = block_sum(sg, sh);
         sgd = block_sum(sgd, sh);
+        float dc = 0.f;
+        if (far) {
+            dc = block_sum(sd, sh) / (float)F;
+            sgd -= dc * sg;
+        }
         const float mg = sg / (float)F;
-        const float k2 = rinv * rinv * sgd / ((float)(F - 1) * stdv);
+        // a row of variance 0: torch's std() backward is 0 where std == 0, so the reference's gradient is the finite
+        // rinv * (g - mean(g)); sgd / stdv is 0 / 0 here.  A select: rows with std > 0 keep their bits.
+        const float k2 = stdv > 0.f ? rinv * rinv * sgd / ((float)(F - 1) * stdv) : 0.f;
         for (long f = threadIdx.x; f < F; f += blockDim.x) {
-            const float d = x[r * F + f] - mu;
+            const float d = (x[r * F + f] - mu) - dc;
             const float dyv = dy[r * F + f];
             dx[r * F + f] = rinv * (dyv * gamma[f] - mg) - k2 * d;
             if (dgx) dgx[r * F + f] = dyv * (d * rinv);
@@ -734,7 +756,7 @@ __global__ __launch_bounds__(256) void ln_last_act_drop_bwd_kernel(const float* 
         sg = pk_wave_sum(sg);
         sgd = pk_wave_sum(sgd);
         const float mg = sg / (float)L;
-        const float k2 = rinv * rinv * sgd / ((float)(L - 1) * stdv);
+        const float k2 = stdv > 0.f ? rinv * rinv * sgd / ((float)(L - 1) * stdv) : 0.f;  // (std == 0: see layernorm_bwd_kernel)
         float* pgx = pg + b * 2 * CL + po;
         for (int f = lane; f < L; f += 64) {
             float g = dy[r * L + f] * pk_act_grad_from_out(act, a[r * L + f]);
@@ -748,6 +770,11 @@ __global__ __launch_bounds__(256) void ln_last_act_drop_bwd_kernel(const float* 
 }
 
 // ---- LogSoftmax(dim=1) -------------------------------------------------------------
+// y = x - (m + log(sum)) rounds the log-sum-exp to an ulp of the row's LEVEL m: logits at 1e4 +- 4 come out 5e-5 off, and
+// exp(y) in the backward pass with them.  Rows whose maximum lies beyond LSM_FAR are written as (x - m) - log(sum) (the
+// first difference is small and nearly exact).  A select on a row-uniform value: rows of ordinary logits keep their bits
+// (the one-ulp difference between the two forms moves a 30-step fp32 training trajectory: tests/test_gpu_reference_pins.py).
+constexpr float LSM_FAR = 32.f;
 __global__ __launch_bounds__(256) void logsoftmax_fwd_kernel(const float* __restrict__ x, long ldx, long rows, long N,
                                                               float* __restrict__ y) {
     __shared__ float sh[8];
@@ -759,8 +786,9 @@ __global__ __launch_bounds__(256) void logsoftmax_fwd_kernel(const float* __rest
         float s = 0.f;
         for (long c = threadIdx.x; c < N; c += blockDim.x) s += expf(xr[c] - m);
         s = block_sum(s, sh);
-        const float lse = m + logf(s);
-        for (long c = threadIdx.x; c < N; c += blockDim.x) y[r * N + c] = xr[c] - lse;
+        const float ls = logf(s), lse = m + ls;
+        const bool far = fabsf(m) > LSM_FAR;  // (see LSM_FAR)
+        for (long c = threadIdx.x; c < N; c += blockDim.x) y[r * N + c] = far ? (xr[c] - m) - ls : xr[c] - lse;
     }
 }
 
@@ -797,11 +825,12 @@ __global__ __launch_bounds__(256) void logsoftmax_fwd_wave_kernel(const float* _
 #pragma unroll
         for (int i = 0; i < NPL; ++i) sum += expf(v[i] - m);  // exp(-inf) = 0 for the padding lanes
         sum = pk_wave_sum(sum);
-        const float lse = m + logf(sum);
+        const float ls = logf(sum), lse = m + ls;
+        const bool far = fabsf(m) > LSM_FAR;  // (see LSM_FAR)
 #pragma unroll
         for (int i = 0; i < NPL; ++i) {
             const long c = lane + 64 * i;
-            v[i] -= lse;
+            v[i] = far ? (v[i] - m) - ls : v[i] - lse;
             if (c < N) y[r * N + c] = v[i];
         }
         if (amax != nullptr) {

@@ -326,7 +326,9 @@ __global__ __launch_bounds__(256) void step_ln_bwd_kernel(StepGeom g, int t, con
     sg = rec_block_sum(sg, sh);
     sgd = rec_block_sum(sgd, sh);
     const float mg = sg / (float)H;
-    const float k2 = rinv * rinv * sgd / ((float)(H - 1) * stdv);
+    // an all-zero state (the first step on a zero-padded frame) has std == 0: torch's std() backward is 0 there, the
+    // reference's gradient is the finite rinv * (g - mean(g)); a select, so that rows with std > 0 keep their bits
+    const float k2 = stdv > 0.f ? rinv * rinv * sgd / ((float)(H - 1) * stdv) : 0.f;
     for (int j = threadIdx.x; j < H; j += blockDim.x) {
         float dh = dyr[j];
         if (carry_h) dh += carry_h[(long)n * H + j];

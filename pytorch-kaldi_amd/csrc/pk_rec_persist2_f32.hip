@@ -564,7 +564,9 @@ __global__ __launch_bounds__(256, 1) void rec2f_bwd_kernel(R2Args a) {
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const float sd = 1.0f / ri4[r] - a.ln_eps;
-                const float k2 = ri4[r] * ri4[r] * lb[r] * inv_nm1 / sd;
+                // (std == 0 - an all-zero state on a zero-padded frame: torch's std() backward is 0 there; a select, so that
+                // rows with std > 0 keep their bits)
+                const float k2 = sd > 0.f ? ri4[r] * ri4[r] * lb[r] * inv_nm1 / sd : 0.f;
                 dh4[r] = ri4[r] * (gg[r] - la[r] * invH) - k2 * dd[r];
             }
         }

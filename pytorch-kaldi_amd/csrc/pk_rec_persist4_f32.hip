@@ -809,7 +809,9 @@ __global__ __launch_bounds__(256, 1) void rec4_bwd_kernel(R2Args a) {
         for (int s_ = 0; s_ < 2; ++s_) {
             const float sa = rh ? la[2 + s_] : la[s_], sb = rh ? lb[2 + s_] : lb[s_];
             const float sd = 1.0f / ri2[s_] - a.ln_eps;
-            const float k2 = ri2[s_] * ri2[s_] * sb * inv_nm1 / sd;
+            // (std == 0 - an all-zero state on a zero-padded frame: torch's std() backward is 0 there; a select, so that rows
+            // with std > 0 keep their bits)
+            const float k2 = sd > 0.f ? ri2[s_] * ri2[s_] * sb * inv_nm1 / sd : 0.f;
             dh2[s_] = ri2[s_] * (gg[s_] - sa * invH) - k2 * dd[s_];
         }
     };

@@ -42,6 +42,32 @@ def rel_err(a, b):
     return float((a - b).norm()) / den
 
 
+def rel_err_rows(a, b, dim):
+    """rel_err of every slice along `dim` (the dimension the norms are taken over: dim=1 grades the rows of a matrix,
+    dim=0 its columns) -> the vector of errors (float64).  A slice whose reference is all zero is graded by the
+    absolute norm of the difference, like rel_err.  A NaN anywhere in a slice makes that slice's error NaN, and
+    `(e < tol).all()` is then False: a NaN cannot pass."""
+    a = a.detach().double().cpu()
+    b = b.detach().double().cpu()
+    assert a.shape == b.shape, (tuple(a.shape), tuple(b.shape))
+    num = (a - b).norm(dim=dim)
+    den = b.norm(dim=dim)
+    return torch.where(den == 0.0, num, num / torch.where(den == 0.0, torch.ones_like(den), den))
+
+
+def rel_err_split(a, b, mask):
+    """(rel_err over the slices picked by `mask`, rel_err over all the others).  mask: bool over the leading dimension(s)
+    of a / b.  A handful of rows with 1e6-sized values dominate a whole-tensor norm and a handful of zero rows vanish
+    in it: grading the two groups separately keeps either from hiding the other.  Both groups must be non-empty.  NaN
+    propagates into the group's figure (NaN < tol is False)."""
+    a = a.detach().cpu()
+    b = b.detach().cpu()
+    mask = mask.cpu()
+    assert mask.dtype == torch.bool and a.shape == b.shape and tuple(mask.shape) == tuple(a.shape[:mask.dim()])
+    assert bool(mask.any()) and not bool(mask.all()), "both groups must hold something"
+    return rel_err(a[mask], b[mask]), rel_err(a[~mask], b[~mask])
+
+
 def grad_err(got, ref, total_norm, floor=1e-3):
     """Gradient check of SURVEY.md Appendix B: norm-relative, except that tensors
     whose gradient is analytically zero (a bias feeding BatchNorm, a conv bias
