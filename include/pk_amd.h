@@ -453,6 +453,22 @@ int pk_fused_step_ex(void* stream, int kind, float* p, float* g, float* s0, floa
                      float h1, float h2, float weight_decay, unsigned flags, int step, int zero_grad, const int64_t* segs,
                      int nseg, uint16_t* shadow);
 
+/* ---- quaternion weight matrices (pk_quat.hip; quaternion_neural_networks.py:378-392).  A quaternion linear layer keeps four
+ * components r, i, j, k, each [I][O] row-major (I = in / 4, O = out / 4).  pk_quat_assemble writes the real matrix it stands
+ * for, for G gates at once, in nn.Linear orientation with the gates stacked row-wise - what the recurrence and GEMM entries
+ * take as W / U:
+ *     W[g*4*O + q*O + o][p*I + i] = S[q][p] * comp[g][q ^ p][i][o]      q, p = 0..3;  r, i, j, k = 0..3
+ *     S = {+ - - -}, {+ + - +}, {+ + + -}, {+ - + +}                    W is [G*4*O][4*I], dense
+ * pk_quat_fold is its transpose, the gradient of the components from dW [G*4*O][4*I]:
+ *     dcomp[g][c][i][o] = beta * dcomp[g][c][i][o] + sum_q S[q][q ^ c] * dW[g*4*O + q*O + o][(q ^ c)*I + i]
+ * with beta 0 (overwrite; the old contents are not read) or 1 (accumulate).  The 4*G components are named EITHER by
+ * `comps` / `dcomps`, a HOST array of 4*G device pointers in the order [g][r, i, j, k], OR by `base` / `dbase` when they lie
+ * back to back in that order in one buffer; the other of the two is NULL.  1 <= G <= PK_QUAT_MAX_GATES, I, O >= 1.
+ * One launch each; 20 bytes moved per component element. */
+#define PK_QUAT_MAX_GATES 8
+int pk_quat_assemble(void* stream, const float* const* comps, const float* base, int G, int I, int O, float* W);
+int pk_quat_fold(void* stream, const float* dW, int G, int I, int O, float beta, float* const* dcomps, float* dbase);
+
 /* persistent-recurrence health: number of spin time-outs since the last reset
  * (host-mapped counter, readable without a device sync). */
 unsigned pk_persist_error_count(void);

@@ -132,6 +132,8 @@ SIGNATURES = {
     "pk_fused_step": (c_int, [P, c_int, P, P, P, P, P, c_int64, c_float, c_float, c_float, c_float, c_float, c_int, c_int, P, c_int, P]),
     "pk_fused_step_ex": (c_int, [P, c_int, P, P, P, P, P, c_int64, c_float, c_float, c_float, c_float, c_float, ctypes.c_uint, c_int,
                                  c_int, P, c_int, P]),
+    "pk_quat_assemble": (c_int, [P, P, P, c_int, c_int, c_int, P]),
+    "pk_quat_fold": (c_int, [P, P, c_int, c_int, c_int, c_float, P, P]),
     "pk_persist_error_count": (ctypes.c_uint, []),
     "pk_persist_error_reset": (None, []),
     "pk_linear_bn_act_bf16_covers": (c_int, [c_int64, c_int64, c_int64]),

@@ -1477,6 +1477,56 @@ def sinc_bank(low_hz, band_hz, n_, window, sample_rate, min_low, min_band):
     return SincBankFn.apply(low_hz, band_hz, n_, window, sample_rate, min_low, min_band)
 
 
+# ----------------------------------------------------------------------------
+# quaternion weight matrices (quaternion_neural_networks.py:378-392)
+# ----------------------------------------------------------------------------
+def _quat_table(ts):
+    """Host array of the tensors' device addresses (what pk_quat_* take as `comps` / `dcomps`) and its address."""
+    arr = (ctypes.c_void_p * len(ts))(*[t.data_ptr() for t in ts])
+    return arr, ctypes.c_void_p(ctypes.addressof(arr))
+
+
+class QuatMatrixFn(torch.autograd.Function):
+    """W = f(comp[0][r], comp[0][i], comp[0][j], comp[0][k], comp[1][r], ..., G, I, O): the real matrix [G*4*O, 4*I] of G
+    quaternion linear layers whose components are [I, O] each, gates stacked row-wise in nn.Linear orientation - what
+    RecLayerFn / RecLayerPerfFn take as Wcat / Ucat (pk_quat_assemble, one launch).  Backward folds dW onto the
+    components (pk_quat_fold, one launch).  Components that lie back to back in one buffer (optim.FlatParams with the
+    module's pk_flat_groups) go in as one base pointer, others as a table of pointers."""
+
+    @staticmethod
+    def forward(ctx, *args):
+        comps, (G, I, O) = args[:-3], (int(a) for a in args[-3:])
+        _need_gpu(*comps)
+        if len(comps) != 4 * G or any(tuple(c.shape) != (I, O) for c in comps):
+            raise _lib.PkError("quaternion matrix: %d gates take %d components of shape (%d, %d), got %s"
+                               % (G, 4 * G, I, O, [tuple(c.shape) for c in comps]))
+        lib = _lib.load()
+        comps = [c.detach().contiguous() for c in comps]
+        W = _new(G * 4 * O, 4 * I, like=comps[0])
+        whole = adjacent_view(comps)
+        if whole is not None:
+            rc = lib.pk_quat_assemble(_stream(), None, _p(whole), G, I, O, _p(W))
+        else:
+            arr, table = _quat_table(comps)
+            rc = lib.pk_quat_assemble(_stream(), table, None, G, I, O, _p(W))
+        _lib.check(rc, "pk_quat_assemble")
+        ctx.cfg = (G, I, O)
+        return W
+
+    @staticmethod
+    def backward(ctx, dW):
+        G, I, O = ctx.cfg
+        lib = _lib.load()
+        dW = dW.contiguous()
+        d = _new(4 * G, I, O, like=dW)
+        _lib.check(lib.pk_quat_fold(_stream(), _p(dW), G, I, O, 0.0, None, _p(d)), "pk_quat_fold")
+        return tuple(d[k] if ctx.needs_input_grad[k] else None for k in range(4 * G)) + (None, None, None)
+
+
+def quat_matrix(comps, G, I, O):
+    return QuatMatrixFn.apply(*comps, G, I, O)
+
+
 class LnLastActDropFn(torch.autograd.Function):
     """drop(act(LayerNorm(z))) behind a conv layer's max-pool as ONE launch each way (pk_ln_last_act_drop_*), the CNN /
     SincNet flavour of the reference's LayerNorm (features [C, L], statistics over the last dim:

@@ -21,6 +21,10 @@ Contract kept from the reference:
     (e.g. neural_networks.py:1102-1107); PK_MASK_RNG=reference draws them with the
     reference's own CPU-RNG call (bit-identical stream), the default draws on the GPU.
 
+``QLSTM`` is the class of the reference's ``quaternion_neural_networks.py`` under the same contract (a recipe that names
+it changes ``arch_library`` from ``quaternion_neural_networks``); its initialisation draws from numpy's global generator,
+as the reference's does.
+
 The nn.Linear / nn.BatchNorm1d / nn.Conv1d sub-modules are parameter containers
 only: ``forward`` never calls them, it hands their tensors to the HIP kernels
 through ``functional``.  There is no CPU path: ``use_cuda`` must be True.
@@ -529,9 +533,30 @@ class _Recurrent(nn.Module):
             out.append(list(self.ln[i].parameters()))
         return out
 
+    def _layer_params(self, i):
+        """(parameters behind the input matrix, parameters behind the recurrent matrix, concatenated bias or None) of layer
+        i, gates in kernel order."""
+        Ws = [getattr(self, w)[i] for (w, _, _) in self._gates]
+        Us = [getattr(self, u)[i] for (_, u, _) in self._gates]
+        bcat = None
+        if Ws[0].bias is not None:
+            bcat = torch.cat([m.bias for m in Ws], 0) if len(Ws) > 1 else Ws[0].bias
+        return [m.weight for m in Ws], [m.weight for m in Us], bcat
+
+    def _layer_matrices(self, wps, ups, perf, edge):
+        """(Wcat, Ucat, side_w, side_u): the gate matrices of one layer as its node takes them (perf: RecLayerPerfFn, else
+        RecLayerFn), and whether their gradients go to the flat .grad from the side stream (the matrix is then handed
+        over without autograd history).  edge: some other input of the node carries the autograd edge."""
+        if perf:
+            side_w, side_u = edge and F_.side_targets_ok(wps), edge and F_.side_targets_ok(ups)
+            view_ok = not torch.is_grad_enabled()
+            return _gate_matrix(wps, False, side_w or view_ok), _gate_matrix(ups, False, side_u or view_ok), side_w, side_u
+        side_w, side_u = edge and F_.side_targets_any_ok(wps), edge and F_.side_targets_any_ok(ups)
+        return _gate_matrix(wps, side_w, side_w), _gate_matrix(ups, side_u, side_u), side_w, side_u
+
     def forward(self, x, drop_masks=None):
         if not x.is_cuda:
-            raise PkError("pytorch-kaldi_amd.nn.%s runs on the GPU only: set use_cuda=True" % self.KIND)
+            raise PkError("pytorch-kaldi_amd.nn.%s runs on the GPU only: set use_cuda=True" % type(self).__name__)
         if self._use_ln_inp:
             x = self.ln0(x)
         if self._use_bn_inp:
@@ -549,15 +574,10 @@ class _Recurrent(nn.Module):
         for i, route in enumerate(routes):
             mask_i, scalar_i = (masks[i], scalars[i]) if masks is not None else self._drop_mask(i, batch, x.device)
             H = self._lay[i]
-            Ws = [getattr(self, w)[i] for (w, _, _) in self._gates]
-            Us = [getattr(self, u)[i] for (_, u, _) in self._gates]
-            wps, ups = [m.weight for m in Ws], [m.weight for m in Us]
-            bcat = None
-            if Ws[0].bias is not None:
-                bcat = torch.cat([m.bias for m in Ws], 0) if len(Ws) > 1 else Ws[0].bias
+            wps, ups, bcat = self._layer_params(i)
             gamma = beta = rmean = rvar = None
             use_bn = bool(self._use_bn[i])
-            bns = [getattr(self, b)[i] for (_, _, b) in self._gates]
+            bns = [getattr(self, b)[i] for (_, _, b) in self._gates] if use_bn else []
             affine = edge_t = None
             if use_bn:
                 gps, bps = [b.weight for b in bns], [b.bias for b in bns]
@@ -586,9 +606,7 @@ class _Recurrent(nn.Module):
             edge = torch.is_grad_enabled() and (use_bn or bcat is not None or x.requires_grad)
             base = (self.KIND, self._act[i], H, bool(self.bidir), use_bn, self.training, 1e-5, 0.05, scalar_i)
             if route.perf:
-                side_w, side_u = edge and F_.side_targets_ok(wps), edge and F_.side_targets_ok(ups)
-                view_ok = not torch.is_grad_enabled()
-                Wcat, Ucat = _gate_matrix(wps, False, side_w or view_ok), _gate_matrix(ups, False, side_u or view_ok)
+                Wcat, Ucat, side_w, side_u = self._layer_matrices(wps, ups, True, edge)
                 # training-mode BatchNorm: the running statistics of every gate's module are updated by the launch that
                 # turns the batch statistics into scale / shift (pk_bn_finalize_gates)
                 stats_in_kernel = use_bn and self.training
@@ -607,9 +625,7 @@ class _Recurrent(nn.Module):
                     continue
             else:
                 # exact-fp32 mode with flat-bucket parameters (round 6): the weight-gradient GEMMs go to the side stream too
-                edge = edge and not F_.bf16_mode()
-                side_w, side_u = edge and F_.side_targets_any_ok(wps), edge and F_.side_targets_any_ok(ups)
-                Wcat, Ucat = _gate_matrix(wps, side_w, side_w), _gate_matrix(ups, side_u, side_u)
+                Wcat, Ucat, side_w, side_u = self._layer_matrices(wps, ups, False, edge and not F_.bf16_mode())
                 lng, lnb = (self.ln[i].gamma, self.ln[i].beta) if self._use_ln[i] else (None, None)
                 y, bmean, bvar = F_.RecLayerFn.apply(x, Wcat, bcat, Ucat, gamma, beta, rmean, rvar, mask_i, lng, lnb,
                                                      F_.RecCfg(*base, wparams=wps, uparams=ups, side_w=side_w, side_u=side_u,
@@ -652,6 +668,125 @@ class LSTM(_Recurrent):
 class RNN(_Recurrent):
     """neural_networks.py:1319-1461."""
     KIND = "RNN"
+
+
+def _chi4(scale, shape):
+    """scipy.stats.chi.rvs(4, loc=0, scale=scale, size=shape) on numpy's global generator; without scipy the draw it
+    makes itself: the root of a chi-square variate with 4 degrees of freedom, scaled."""
+    try:
+        from scipy.stats import chi
+    except ImportError:
+        return scale * np.sqrt(np.random.chisquare(4, size=shape))
+    return chi.rvs(4, loc=0, scale=scale, size=shape)
+
+
+class _QuatLinear(nn.Module):
+    """Parameter container of one quaternion linear layer (quaternion_neural_networks.py:223-280): four components
+    [in / 4, out / 4] and, for the input projections, a bias [out].  forward never calls it: QLSTM assembles the real
+    matrices of a layer's gates with functional.quat_matrix.  The initialisation is the reference's 'quaternion' /
+    'glorot' (:574-647) and consumes numpy's GLOBAL generator in its order - the layer's seed (:247, drawn and not used
+    by this initialiser), the seed of the phase generator (:591), the chi(4) moduli, three normal vectors - so that
+    np.random.seed gives the reference's weights."""
+
+    def __init__(self, in_features, out_features, bias=True):
+        super().__init__()
+        self.in_features, self.out_features = in_features // 4, out_features // 4
+        shape = (self.in_features, self.out_features)
+        self.seed = np.random.randint(0, 1234)
+        rng = np.random.RandomState(np.random.randint(1, 1234))
+        s = 1.0 / np.sqrt(2 * (shape[0] + shape[1]))
+        modulus = _chi4(s, shape)
+        n = shape[0] * shape[1]
+        v_i, v_j, v_k = (np.random.normal(0, 1.0, n) for _ in range(3))
+        norm = np.sqrt(v_i ** 2 + v_j ** 2 + v_k ** 2 + 0.0001)  # (the reference's element loop, all elements at once)
+        v_i, v_j, v_k = ((v / norm).reshape(shape) for v in (v_i, v_j, v_k))
+        phase = rng.uniform(low=-np.pi, high=np.pi, size=shape)
+        comps = (modulus * np.cos(phase), modulus * v_i * np.sin(phase), modulus * v_j * np.sin(phase),
+                 modulus * v_k * np.sin(phase))
+        for name, w in zip(("r_weight", "i_weight", "j_weight", "k_weight"), comps):
+            setattr(self, name, nn.Parameter(torch.from_numpy(w).float()))
+        if bias:
+            self.bias = nn.Parameter(torch.zeros(self.out_features * 4))
+        else:
+            self.register_parameter("bias", None)
+
+    def components(self):
+        return [self.r_weight, self.i_weight, self.j_weight, self.k_weight]
+
+
+class QLSTM(_Recurrent):
+    """quaternion_neural_networks.py:21-168: the reference's LSTM without normalisation and with a bias on every input
+    projection, every weight matrix being the real form of a quaternion matrix (four components of a sixteenth of its
+    size each).  The recurrence, the projections and their gradients are the LSTM's own kernels on the assembled
+    matrices (functional.QuatMatrixFn: one assembly launch per matrix and forward, one fold launch per matrix and
+    backward); weight gradients come back through autograd, on the main stream.  `autograd` selects between two forms of
+    the same function in the reference and changes nothing here; `quaternion_init` is ignored as it is there."""
+    KIND = "LSTM"
+
+    def __init__(self, options, inp_dim):
+        # (not _Recurrent's constructor: other option fields, other sub-modules; what follows sets what its forward,
+        # _drop_mask and flat-layout code read)
+        nn.Module.__init__(self)
+        self._pre = "lstm"
+        self._gates = [("wfx", "ufh", None), ("wix", "uih", None), ("wox", "uoh", None), ("wcx", "uch", None)]
+        self.input_dim = inp_dim
+        self.lstm_lay = self._lay = _ints(_opt(options, "lstm_lay"))
+        self.lstm_drop = self._drop = _floats(_opt(options, "lstm_drop"))
+        self.lstm_act = self._act = str(_opt(options, "lstm_act")).split(",")
+        self.bidir = strtobool(_opt(options, "lstm_bidir"))
+        self.use_cuda = strtobool(_opt(options, "use_cuda"))
+        self.autograd = strtobool(_opt(options, "autograd"))
+        self.to_do = _opt(options, "to_do")
+        self.test_flag = self.to_do != "train"
+        self.N_lstm_lay = self._n_lay = len(self._lay)
+        self._use_bn = self._use_ln = [0] * self._n_lay
+        self._use_bn_inp = self._use_ln_inp = 0
+        for a in self._act:
+            if a not in F_.ACT:
+                raise PkError("QLSTM: activation %r is not supported inside the recurrence" % (a,))
+        for width in [inp_dim] + self._lay:  # (the reference fails at the first forward call: check_input, :325-339)
+            if width < 4 or width % 4 != 0:
+                raise PkError("QLSTM: input and layer widths must be multiples of 4 (got input %d, lstm_lay %s)"
+                              % (inp_dim, self._lay))
+        # registration order = the reference's (:51-63); construction order inside a layer = the reference's too (:94-103),
+        # which is the order the initialisers draw from numpy's generator
+        for name in ("wfx", "ufh", "wix", "uih", "wox", "uoh", "wcx", "uch", "act"):
+            setattr(self, name, nn.ModuleList([]))
+        cur = self.input_dim
+        for i in range(self._n_lay):
+            self.act.append(act_fun(self._act[i]))
+            for name in ("wfx", "wix", "wox", "wcx"):
+                getattr(self, name).append(_QuatLinear(cur, self._lay[i], bias=True))
+            for name in ("ufh", "uih", "uoh", "uch"):
+                getattr(self, name).append(_QuatLinear(self._lay[i], self._lay[i], bias=False))
+            cur = 2 * self._lay[i] if self.bidir else self._lay[i]
+        self.out_dim = self._lay[-1] + self.bidir * self._lay[-1]
+
+    def pk_unused_parameters(self):
+        return []
+
+    def _layer_comps(self, i):
+        ws = [q for (w, _, _) in self._gates for q in getattr(self, w)[i].components()]
+        us = [q for (_, u, _) in self._gates for q in getattr(self, u)[i].components()]
+        return ws, us
+
+    def pk_flat_groups(self):
+        """optim.FlatParams layout: layer by layer the 16 components of the input matrices (gates f, i, o, c; r, i, j, k
+        inside a gate) back to back, the 16 of the recurrent matrices, the four biases: pk_quat_assemble then takes
+        each group as one base pointer."""
+        out = []
+        for i in range(self._n_lay):
+            ws, us = self._layer_comps(i)
+            out += [ws, us, [getattr(self, w)[i].bias for (w, _, _) in self._gates]]
+        return out
+
+    def _layer_params(self, i):
+        ws, us = self._layer_comps(i)
+        return ws, us, torch.cat([getattr(self, w)[i].bias for (w, _, _) in self._gates], 0)
+
+    def _layer_matrices(self, wps, ups, perf, edge):
+        G = len(self._gates)
+        return (F_.quat_matrix(wps, G, *wps[0].shape), F_.quat_matrix(ups, G, *ups[0].shape), False, False)
 
 
 class SincConv(nn.Module):
