@@ -469,6 +469,42 @@ int pk_fused_step_ex(void* stream, int kind, float* p, float* g, float* s0, floa
 int pk_quat_assemble(void* stream, const float* const* comps, const float* base, int G, int I, int O, float* W);
 int pk_quat_fold(void* stream, const float* dW, int G, int I, int O, float beta, float* const* dcomps, float* dbase);
 
+/* ---- torch-layout recurrent layers on the engine's cells (pk_pack.hip; the cuDNN wrappers, neural_networks.py:153-203 and
+ * :256-297).  torch.nn.LSTM / nn.RNN keep, per layer and direction, weight_ih [G*H][D], weight_hh [G*H][H] and two biases
+ * [G*H] with the gate blocks in torch's order (LSTM: i, f, g, o); the recurrence entries take Wcat / Ucat / one bias in the
+ * kernels' order (PK_CELL_LSTM: f, i, o, c).  perm [G] (host): engine gate g is torch block perm[g] - {1, 0, 3, 2} for the
+ * LSTM, {0} for the RNN.
+ *   pk_gates_pack     Wcat[g*H + r][:] = w_ih[perm[g]*H + r][:], Ucat likewise from w_hh, bcat = b_ih + b_hh (one fp32 add;
+ *                     one bias NULL: a copy of the other; both NULL: bcat is not written).  Replaces what cuDNN / MIOpen do
+ *                     behind self.lstm[0](x, (h0, c0)) (:201) when they flatten the weights.
+ *   pk_gates_unpack   the transpose: block g of dWcat / dUcat goes to block perm[g] of dw_ih / dw_hh, dbcat to db_ih and to
+ *                     db_hh (either may be NULL).  Every destination element is written once: nothing is accumulated.
+ * A matrix and its destination may both be NULL (the RNN hands its single block over as it is and only sums the biases).
+ * 1 <= G <= PK_PACK_MAX_GATES; H, D >= 1.  One launch; 8 bytes moved per matrix element.
+ *   pk_seq_join_fwd   the output of a (bi)directional layer with the dropout torch applies between layers (:172, a fresh
+ *                     Bernoulli draw per element, scaled): yf [T][B][H] in time order, yb [T][B][H] in REVERSED time order
+ *                     (the backward direction runs on the time-reversed input; NULL iff ndir == 1), mask [T][B][ndir*H] of
+ *                     0 / 1 floats or NULL, at the position of the output element:
+ *                         y[t][b][0:H]  = mask ? yf[t][b][:] * scale : 0
+ *                         y[t][b][H:2H] = mask ? yb[T-1-t][b][:] * scale : 0          (no mask: every element is kept)
+ *                         y_rev[t] = y[T-1-t]     the next layer's backward-direction input, from the same read
+ *                     One of y / y_rev may be NULL, not both.  ndir = 1 without mask and y is a plain time reversal.
+ *   pk_seq_join_bwd   dyf[t] = mask * scale * (dy[t][0:H] + dy_rev[T-1-t][0:H]), dyb[s] = mask * scale * (dy[T-1-s][H:2H] +
+ *                     dy_rev[s][H:2H]), the mask taken at the y position; dy or dy_rev may be NULL (not both), and then
+ *                     nothing is added.
+ * T, B, H >= 1, ndir 1 or 2.  One launch each; 4 bytes read and 4 (8 with both outputs) written per output element, plus 4
+ * for the mask.  16-byte accesses when H (and D for the gates) is a multiple of 4 and every pointer is 16-byte aligned, scalar
+ * ones otherwise.  Bad arguments return 2 and launch nothing. */
+#define PK_PACK_MAX_GATES 8
+int pk_gates_pack(void* stream, const float* w_ih, const float* w_hh, const float* b_ih, const float* b_hh, int G, int H, int D,
+                  const int* perm, float* Wcat, float* Ucat, float* bcat);
+int pk_gates_unpack(void* stream, const float* dWcat, const float* dUcat, const float* dbcat, int G, int H, int D,
+                    const int* perm, float* dw_ih, float* dw_hh, float* db_ih, float* db_hh);
+int pk_seq_join_fwd(void* stream, const float* yf, const float* yb, const float* mask, float scale, int64_t T, int64_t B,
+                    int64_t H, int ndir, float* y, float* y_rev);
+int pk_seq_join_bwd(void* stream, const float* dy, const float* dy_rev, const float* mask, float scale, int64_t T, int64_t B,
+                    int64_t H, int ndir, float* dyf, float* dyb);
+
 /* persistent-recurrence health: number of spin time-outs since the last reset
  * (host-mapped counter, readable without a device sync). */
 unsigned pk_persist_error_count(void);

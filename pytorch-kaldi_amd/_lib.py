@@ -134,6 +134,10 @@ SIGNATURES = {
                                  c_int, P, c_int, P]),
     "pk_quat_assemble": (c_int, [P, P, P, c_int, c_int, c_int, P]),
     "pk_quat_fold": (c_int, [P, P, c_int, c_int, c_int, c_float, P, P]),
+    "pk_gates_pack": (c_int, [P, P, P, P, P, c_int, c_int, c_int, P, P, P, P]),
+    "pk_gates_unpack": (c_int, [P, P, P, P, c_int, c_int, c_int, P, P, P, P, P]),
+    "pk_seq_join_fwd": (c_int, [P, P, P, P, c_float, c_int64, c_int64, c_int64, c_int, P, P]),
+    "pk_seq_join_bwd": (c_int, [P, P, P, P, c_float, c_int64, c_int64, c_int64, c_int, P, P]),
     "pk_persist_error_count": (ctypes.c_uint, []),
     "pk_persist_error_reset": (None, []),
     "pk_linear_bn_act_bf16_covers": (c_int, [c_int64, c_int64, c_int64]),

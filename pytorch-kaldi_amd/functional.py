@@ -1527,6 +1527,127 @@ def quat_matrix(comps, G, I, O):
     return QuatMatrixFn.apply(*comps, G, I, O)
 
 
+# ----------------------------------------------------------------------------
+# torch-layout recurrent layers (the cuDNN wrappers, neural_networks.py:153-203, :256-297)
+# ----------------------------------------------------------------------------
+GATE_PERM = {"LSTM": (1, 0, 3, 2), "RNN": (0,)}  # engine gate g (LSTM: f, i, o, c) is torch block GATE_PERM[g] (i, f, g, o)
+
+
+def _perm_arg(perm):
+    return (ctypes.c_int * len(perm))(*perm)
+
+
+class GatesPackFn(torch.autograd.Function):
+    """Wcat, Ucat, bcat = f(w_ih, w_hh, b_ih, b_hh, perm): the gate blocks of one torch-layout layer and direction in the
+    kernels' order, the two biases summed (pk_gates_pack, one launch); backward is pk_gates_unpack, one launch, which gives
+    both biases the same gradient.  w_ih and w_hh may both be None (one gate: the caller hands the matrices over as they
+    are) and so may either bias; an output whose inputs are all None is None."""
+
+    @staticmethod
+    def forward(ctx, w_ih, w_hh, b_ih, b_hh, perm):
+        _need_gpu(w_ih, w_hh, b_ih, b_hh)
+        if (w_ih is None) != (w_hh is None):
+            raise _lib.PkError("gates_pack: weight_ih and weight_hh go together")
+        lib = _lib.load()
+        G = len(perm)
+        like = next(t for t in (w_ih, b_ih, b_hh) if t is not None)
+        if w_ih is not None:
+            H, D = w_hh.shape[1], w_ih.shape[1]
+            if tuple(w_ih.shape) != (G * H, D) or tuple(w_hh.shape) != (G * H, H):
+                raise _lib.PkError("gates_pack: %d gates of width %d take [%d, D] and [%d, %d], got %s and %s"
+                                   % (G, H, G * H, G * H, H, tuple(w_ih.shape), tuple(w_hh.shape)))
+            w_ih, w_hh = w_ih.detach().contiguous(), w_hh.detach().contiguous()
+        else:
+            H, D = like.shape[0] // G, 1
+        for b_ in (b_ih, b_hh):
+            if b_ is not None and tuple(b_.shape) != (G * H,):
+                raise _lib.PkError("gates_pack: a bias of %d gates of width %d is [%d], got %s" % (G, H, G * H, tuple(b_.shape)))
+        b_ih = None if b_ih is None else b_ih.detach().contiguous()
+        b_hh = None if b_hh is None else b_hh.detach().contiguous()
+        Wcat = Ucat = bcat = None
+        if w_ih is not None:
+            Wcat, Ucat = _new(G * H, D, like=like), _new(G * H, H, like=like)
+        if b_ih is not None or b_hh is not None:
+            bcat = _new(G * H, like=like)
+        _lib.check(lib.pk_gates_pack(_stream(), _p(w_ih), _p(w_hh), _p(b_ih), _p(b_hh), G, H, D, _perm_arg(perm), _p(Wcat),
+                                     _p(Ucat), _p(bcat)), "pk_gates_pack")
+        ctx.cfg = (G, H, D, tuple(perm), w_ih is not None, b_ih is not None, b_hh is not None)
+        return Wcat, Ucat, bcat
+
+    @staticmethod
+    def backward(ctx, dW, dU, db):
+        G, H, D, perm, has_w, has_bi, has_bh = ctx.cfg
+        lib = _lib.load()
+        like = next(t for t in (dW, db) if t is not None)
+        dw_ih = dw_hh = db_ih = db_hh = None
+        if has_w:
+            dW, dU = dW.contiguous(), dU.contiguous()
+            dw_ih, dw_hh = _new(G * H, D, like=like), _new(G * H, H, like=like)
+        if has_bi or has_bh:
+            db = db.contiguous()
+            db_ih = _new(G * H, like=like) if has_bi else None
+            db_hh = _new(G * H, like=like) if has_bh else None
+        _lib.check(lib.pk_gates_unpack(_stream(), _p(dW) if has_w else None, _p(dU) if has_w else None,
+                                       _p(db) if (has_bi or has_bh) else None, G, H, D, _perm_arg(perm), _p(dw_ih), _p(dw_hh),
+                                       _p(db_ih), _p(db_hh)), "pk_gates_unpack")
+        return dw_ih, dw_hh, db_ih, db_hh, None
+
+
+def gates_pack(w_ih, w_hh, b_ih, b_hh, perm):
+    return GatesPackFn.apply(w_ih, w_hh, b_ih, b_hh, tuple(perm))
+
+
+class SeqJoinFn(torch.autograd.Function):
+    """y, y_rev = f(yf, yb, mask, scale, want_y, want_rev): the two directions of a layer joined along the features (yb comes
+    in reversed time order and is turned round; None: one direction), the inter-layer dropout mask [T, B, ndir*H] of 0 / 1
+    applied with its scale (None: every element kept), and on request the same tensor reversed in time - the next layer's
+    backward-direction input (pk_seq_join_fwd / _bwd, one launch each way).  An output that was not asked for is None."""
+
+    @staticmethod
+    def forward(ctx, yf, yb, mask, scale, want_y, want_rev):
+        ctx.set_materialize_grads(False)
+        _need_gpu(yf, yb, mask)
+        if not (want_y or want_rev):
+            raise _lib.PkError("seq_join: neither the joined tensor nor its time reversal is asked for")
+        lib = _lib.load()
+        T, B, H = yf.shape
+        ndir = 1 if yb is None else 2
+        if yb is not None and yb.shape != yf.shape:
+            raise _lib.PkError("seq_join: the directions differ in shape: %s and %s" % (tuple(yf.shape), tuple(yb.shape)))
+        if mask is not None and tuple(mask.shape) != (T, B, ndir * H):
+            raise _lib.PkError("seq_join: the mask of a [%d, %d, %d] output is %s" % (T, B, ndir * H, tuple(mask.shape)))
+        yf = yf.detach().contiguous()
+        yb = None if yb is None else yb.detach().contiguous()
+        mask = None if mask is None else mask.contiguous()
+        y = _new(T, B, ndir * H, like=yf) if want_y else None
+        y_rev = _new(T, B, ndir * H, like=yf) if want_rev else None
+        _lib.check(lib.pk_seq_join_fwd(_stream(), _p(yf), _p(yb), _p(mask), float(scale), T, B, H, ndir, _p(y), _p(y_rev)),
+                   "pk_seq_join_fwd")
+        ctx.save_for_backward(mask)
+        ctx.cfg = (float(scale), T, B, H, ndir)
+        return y, y_rev
+
+    @staticmethod
+    def backward(ctx, dy, dy_rev):
+        if dy is None and dy_rev is None:
+            return (None,) * 6
+        scale, T, B, H, ndir = ctx.cfg
+        mask, = ctx.saved_tensors
+        lib = _lib.load()
+        dy = None if dy is None else dy.contiguous()
+        dy_rev = None if dy_rev is None else dy_rev.contiguous()
+        like = dy if dy is not None else dy_rev
+        dyf = _new(T, B, H, like=like)
+        dyb = _new(T, B, H, like=like) if ndir == 2 else None
+        _lib.check(lib.pk_seq_join_bwd(_stream(), _p(dy), _p(dy_rev), _p(mask), scale, T, B, H, ndir, _p(dyf), _p(dyb)),
+                   "pk_seq_join_bwd")
+        return dyf, dyb, None, None, None, None
+
+
+def seq_join(yf, yb=None, mask=None, scale=1.0, want_y=True, want_rev=False):
+    return SeqJoinFn.apply(yf, yb, mask, scale, want_y, want_rev)
+
+
 class LnLastActDropFn(torch.autograd.Function):
     """drop(act(LayerNorm(z))) behind a conv layer's max-pool as ONE launch each way (pk_ln_last_act_drop_*), the CNN /
     SincNet flavour of the reference's LayerNorm (features [C, L], statistics over the last dim:

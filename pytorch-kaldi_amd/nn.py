@@ -25,6 +25,10 @@ Contract kept from the reference:
 it changes ``arch_library`` from ``quaternion_neural_networks``); its initialisation draws from numpy's global generator,
 as the reference's does.
 
+``LSTM_cudnn`` / ``RNN_cudnn`` (neural_networks.py:153-203, :256-297) keep torch.nn.LSTM / nn.RNN's parameter names, layout and
+initialisation and run on the LSTM / RNN cells, one direction per launch; ``GRU_cudnn`` raises: nn.GRU's cell is none of the
+engine's.
+
 The nn.Linear / nn.BatchNorm1d / nn.Conv1d sub-modules are parameter containers
 only: ``forward`` never calls them, it hands their tensors to the HIP kernels
 through ``functional``.  There is no CPU path: ``use_cuda`` must be True.
@@ -554,6 +558,76 @@ class _Recurrent(nn.Module):
         side_w, side_u = edge and F_.side_targets_any_ok(wps), edge and F_.side_targets_any_ok(ups)
         return _gate_matrix(wps, side_w, side_w), _gate_matrix(ups, side_u, side_u), side_w, side_u
 
+    def _layer(self, i, x, xb, xseg, mask_i, scalar_i, route, keep_y):
+        """Layer i on x: (y, bf16 copy of y or None, its segments).  xb / xseg: the bf16 copy the layer below published
+        (perf node), mask_i / scalar_i: the drop mask, keep_y: functional.rec_keep_y."""
+        H = self._lay[i]
+        wps, ups, bcat = self._layer_params(i)
+        gamma = beta = rmean = rvar = None
+        use_bn = bool(self._use_bn[i])
+        bns = [getattr(self, b)[i] for (_, _, b) in self._gates] if use_bn else []
+        affine = edge_t = None
+        if use_bn:
+            gps, bps = [b.weight for b in bns], [b.bias for b in bns]
+            if self.training and F_.direct_affine_ok(gps + bps) and route.perf:
+                # the engine's own training step: scales / shifts as views of the flat buffer (no concatenation
+                # launches), their gradients added to the flat .grad by the BatchNorm backward itself
+                gamma, beta = F_.adjacent_view([q.detach() for q in gps]), F_.adjacent_view([q.detach() for q in bps])
+                if (gamma is not None and beta is not None and F_.adjacent_view([q.grad for q in gps]) is not None
+                        and F_.adjacent_view([q.grad for q in bps]) is not None):
+                    affine, edge_t = (gps, bps), gps[0]  # (the first scale carries the autograd edge, gradient None)
+            if affine is None:
+                gamma = torch.cat(gps, 0)
+                beta = torch.cat(bps, 0)
+            if not self.training:
+                rmean = torch.cat([b.running_mean for b in bns], 0)
+                rvar = torch.cat([b.running_var for b in bns], 0)
+        if use_bn and self.training and x.shape[0] * x.shape[1] * (2 if self.bidir else 1) <= 1:
+            # what torch's BatchNorm1d raises for the reference in the same situation (one row, training mode)
+            raise ValueError("Expected more than 1 value per channel when training, got input size %s"
+                             % (tuple(x.shape),))
+        # weight gradients that go to the flat .grad buffer from the side stream do not pass through autograd: the
+        # concatenated weights are handed over detached (otherwise cat's backward materialises a zero gradient per gate
+        # and adds it to .grad on the main stream - launches, and a write that would race a data-parallel bucket
+        # already being reduced).  Some other input must still carry the autograd edge that makes backward run at all:
+        # the BatchNorm affine or the bias - one of the two always exists, neural_networks.py:1052-1055 - or x itself
+        edge = torch.is_grad_enabled() and (use_bn or bcat is not None or x.requires_grad)
+        base = (self.KIND, self._act[i], H, bool(self.bidir), use_bn, self.training, 1e-5, 0.05, scalar_i)
+        if route.perf:
+            Wcat, Ucat, side_w, side_u = self._layer_matrices(wps, ups, True, edge)
+            # training-mode BatchNorm: the running statistics of every gate's module are updated by the launch that
+            # turns the batch statistics into scale / shift (pk_bn_finalize_gates)
+            stats_in_kernel = use_bn and self.training
+            bn_bufs = ([b.running_mean for b in bns], [b.running_var for b in bns],
+                       [b.num_batches_tracked for b in bns]) if stats_in_kernel else None
+            # forward-only chunks: an inner layer's fp32 output is read by nobody when the next layer is a perf node too
+            # (it takes the bf16 copy; the general node reads the fp32 tensor): functional.rec_keep_y
+            cfg = F_.RecCfg(*base, xseg=xseg, wparams=wps, uparams=ups, side_w=side_w, side_u=side_u, bn_bufs=bn_bufs,
+                            affine=affine, keep_y=keep_y, route=route)
+            y, bmean, bvar, xb = F_.RecLayerPerfFn.apply(x, xb, Wcat.detach() if side_w else Wcat, bcat,
+                                                       Ucat.detach() if side_u else Ucat, gamma, beta, rmean, rvar,
+                                                       mask_i, cfg, edge_t)
+            xseg = (2 if self.bidir else 1, H, (H + 7) // 8 * 8)
+            if stats_in_kernel:
+                return y, xb, xseg
+        else:
+            # exact-fp32 mode with flat-bucket parameters (round 6): the weight-gradient GEMMs go to the side stream too
+            Wcat, Ucat, side_w, side_u = self._layer_matrices(wps, ups, False, edge and not F_.bf16_mode())
+            lng, lnb = (self.ln[i].gamma, self.ln[i].beta) if self._use_ln[i] else (None, None)
+            y, bmean, bvar = F_.RecLayerFn.apply(x, Wcat, bcat, Ucat, gamma, beta, rmean, rvar, mask_i, lng, lnb,
+                                                 F_.RecCfg(*base, wparams=wps, uparams=ups, side_w=side_w, side_u=side_u,
+                                                           route=route))
+            xb = xseg = None
+        if use_bn and self.training:
+            n = x.shape[0] * x.shape[1] * (2 if self.bidir else 1)
+            with torch.no_grad():  # BatchNorm1d(momentum=0.05) running statistics, per gate: four multi-tensor launches
+                means, vars_ = [b.running_mean for b in bns], [b.running_var for b in bns]
+                torch._foreach_mul_(means + vars_, 0.95)
+                torch._foreach_add_(means, [bmean[k * H:(k + 1) * H] for k in range(len(bns))], alpha=0.05)
+                torch._foreach_add_(vars_, [bvar[k * H:(k + 1) * H] for k in range(len(bns))], alpha=0.05 * n / (n - 1))
+                torch._foreach_add_([b.num_batches_tracked for b in bns], 1)
+        return y, xb, xseg
+
     def forward(self, x, drop_masks=None):
         if not x.is_cuda:
             raise PkError("pytorch-kaldi_amd.nn.%s runs on the GPU only: set use_cuda=True" % type(self).__name__)
@@ -573,73 +647,8 @@ class _Recurrent(nn.Module):
                   for i in range(self._n_lay)]
         for i, route in enumerate(routes):
             mask_i, scalar_i = (masks[i], scalars[i]) if masks is not None else self._drop_mask(i, batch, x.device)
-            H = self._lay[i]
-            wps, ups, bcat = self._layer_params(i)
-            gamma = beta = rmean = rvar = None
-            use_bn = bool(self._use_bn[i])
-            bns = [getattr(self, b)[i] for (_, _, b) in self._gates] if use_bn else []
-            affine = edge_t = None
-            if use_bn:
-                gps, bps = [b.weight for b in bns], [b.bias for b in bns]
-                if self.training and F_.direct_affine_ok(gps + bps) and route.perf:
-                    # the engine's own training step: scales / shifts as views of the flat buffer (no concatenation
-                    # launches), their gradients added to the flat .grad by the BatchNorm backward itself
-                    gamma, beta = F_.adjacent_view([q.detach() for q in gps]), F_.adjacent_view([q.detach() for q in bps])
-                    if (gamma is not None and beta is not None and F_.adjacent_view([q.grad for q in gps]) is not None
-                            and F_.adjacent_view([q.grad for q in bps]) is not None):
-                        affine, edge_t = (gps, bps), gps[0]  # (the first scale carries the autograd edge, gradient None)
-                if affine is None:
-                    gamma = torch.cat(gps, 0)
-                    beta = torch.cat(bps, 0)
-                if not self.training:
-                    rmean = torch.cat([b.running_mean for b in bns], 0)
-                    rvar = torch.cat([b.running_var for b in bns], 0)
-            if use_bn and self.training and x.shape[0] * x.shape[1] * (2 if self.bidir else 1) <= 1:
-                # what torch's BatchNorm1d raises for the reference in the same situation (one row, training mode)
-                raise ValueError("Expected more than 1 value per channel when training, got input size %s"
-                                 % (tuple(x.shape),))
-            # weight gradients that go to the flat .grad buffer from the side stream do not pass through autograd: the
-            # concatenated weights are handed over detached (otherwise cat's backward materialises a zero gradient per gate
-            # and adds it to .grad on the main stream - launches, and a write that would race a data-parallel bucket
-            # already being reduced).  Some other input must still carry the autograd edge that makes backward run at all:
-            # the BatchNorm affine or the bias - one of the two always exists, neural_networks.py:1052-1055 - or x itself
-            edge = torch.is_grad_enabled() and (use_bn or bcat is not None or x.requires_grad)
-            base = (self.KIND, self._act[i], H, bool(self.bidir), use_bn, self.training, 1e-5, 0.05, scalar_i)
-            if route.perf:
-                Wcat, Ucat, side_w, side_u = self._layer_matrices(wps, ups, True, edge)
-                # training-mode BatchNorm: the running statistics of every gate's module are updated by the launch that
-                # turns the batch statistics into scale / shift (pk_bn_finalize_gates)
-                stats_in_kernel = use_bn and self.training
-                bn_bufs = ([b.running_mean for b in bns], [b.running_var for b in bns],
-                           [b.num_batches_tracked for b in bns]) if stats_in_kernel else None
-                # forward-only chunks: an inner layer's fp32 output is read by nobody when the next layer is a perf node too
-                # (it takes the bf16 copy; the general node reads the fp32 tensor): functional.rec_keep_y
-                cfg = F_.RecCfg(*base, xseg=xseg, wparams=wps, uparams=ups, side_w=side_w, side_u=side_u, bn_bufs=bn_bufs,
-                                affine=affine, keep_y=F_.rec_keep_y(routes, i, torch.is_grad_enabled()), route=route)
-                y, bmean, bvar, xb = F_.RecLayerPerfFn.apply(x, xb, Wcat.detach() if side_w else Wcat, bcat,
-                                                           Ucat.detach() if side_u else Ucat, gamma, beta, rmean, rvar,
-                                                           mask_i, cfg, edge_t)
-                xseg = (2 if self.bidir else 1, H, (H + 7) // 8 * 8)
-                if stats_in_kernel:
-                    x = y
-                    continue
-            else:
-                # exact-fp32 mode with flat-bucket parameters (round 6): the weight-gradient GEMMs go to the side stream too
-                Wcat, Ucat, side_w, side_u = self._layer_matrices(wps, ups, False, edge and not F_.bf16_mode())
-                lng, lnb = (self.ln[i].gamma, self.ln[i].beta) if self._use_ln[i] else (None, None)
-                y, bmean, bvar = F_.RecLayerFn.apply(x, Wcat, bcat, Ucat, gamma, beta, rmean, rvar, mask_i, lng, lnb,
-                                                     F_.RecCfg(*base, wparams=wps, uparams=ups, side_w=side_w, side_u=side_u,
-                                                               route=route))
-                xb = xseg = None
-            if use_bn and self.training:
-                n = x.shape[0] * x.shape[1] * (2 if self.bidir else 1)
-                with torch.no_grad():  # BatchNorm1d(momentum=0.05) running statistics, per gate: four multi-tensor launches
-                    means, vars_ = [b.running_mean for b in bns], [b.running_var for b in bns]
-                    torch._foreach_mul_(means + vars_, 0.95)
-                    torch._foreach_add_(means, [bmean[k * H:(k + 1) * H] for k in range(len(bns))], alpha=0.05)
-                    torch._foreach_add_(vars_, [bvar[k * H:(k + 1) * H] for k in range(len(bns))], alpha=0.05 * n / (n - 1))
-                    torch._foreach_add_([b.num_batches_tracked for b in bns], 1)
-            x = y
+            x, xb, xseg = self._layer(i, x, xb, xseg, mask_i, scalar_i, route,
+                                      F_.rec_keep_y(routes, i, torch.is_grad_enabled()))
         if xb is not None:  # the bf16 copy the last layer published: a perf-mode Linear behind it uses it as its operand
             x._pk_twin = (xb, xseg, x._version)
         return x
@@ -787,6 +796,170 @@ class QLSTM(_Recurrent):
     def _layer_matrices(self, wps, ups, perf, edge):
         G = len(self._gates)
         return (F_.quat_matrix(wps, G, *wps[0].shape), F_.quat_matrix(ups, G, *ups[0].shape), False, False)
+
+
+class _TorchRnnParams(nn.Module):
+    """Parameter container with the names, shapes, registration order and initial values of torch.nn.LSTM / nn.RNN
+    (weight_ih_l{k}[_reverse] [G*H, in], weight_hh_l{k}[_reverse] [G*H, H], bias_ih / bias_hh [G*H]; every parameter
+    uniform(-1/sqrt(H), 1/sqrt(H)) in registration order, torch's reset_parameters).  It is not a torch.nn.LSTM: that
+    module's _apply re-flattens the weights through MIOpen on .cuda(), and nothing here ever calls its forward."""
+
+    def __init__(self, gates, input_size, hidden_size, num_layers, bias, bidirectional):
+        super().__init__()
+        ndir = 2 if bidirectional else 1
+        for k in range(num_layers):
+            cur = input_size if k == 0 else ndir * hidden_size
+            for d in range(ndir):
+                sfx = "_l%d%s" % (k, "_reverse" if d else "")
+                self.register_parameter("weight_ih" + sfx, nn.Parameter(torch.empty(gates * hidden_size, cur)))
+                self.register_parameter("weight_hh" + sfx, nn.Parameter(torch.empty(gates * hidden_size, hidden_size)))
+                if bias:
+                    self.register_parameter("bias_ih" + sfx, nn.Parameter(torch.empty(gates * hidden_size)))
+                    self.register_parameter("bias_hh" + sfx, nn.Parameter(torch.empty(gates * hidden_size)))
+        stdv = 1.0 / math.sqrt(hidden_size) if hidden_size > 0 else 0
+        for q in self.parameters():
+            nn.init.uniform_(q, -stdv, stdv)
+
+    def of(self, k, d):
+        """(weight_ih, weight_hh, bias_ih or None, bias_hh or None) of layer k, direction d."""
+        sfx = "_l%d%s" % (k, "_reverse" if d else "")
+        return tuple(getattr(self, n + sfx, None) for n in ("weight_ih", "weight_hh", "bias_ih", "bias_hh"))
+
+
+class _Cudnn(_Recurrent):
+    """Shared body of LSTM_cudnn / RNN_cudnn (neural_networks.py:153-203, :256-297): torch.nn.LSTM / nn.RNN on the engine's
+    LSTM / RNN cells.  Every (layer, direction) is one unidirectional layer of _Recurrent._layer - no normalisation, no
+    recurrent mask, the routes of functional.rec_route - on gate matrices packed into the kernels' order
+    (functional.gates_pack); the backward direction runs on the time-reversed input, and functional.seq_join puts the two
+    outputs together, applies torch's inter-layer dropout and writes the next layer's reversed input in the same pass.  The
+    two directions run one after the other on one stream.  Weight gradients come back through autograd, on the main stream;
+    no bf16 copy is handed from layer to layer (it would have to cross the join)."""
+    KIND = ATTR = None
+
+    def _setup(self, options, inp_dim, act):
+        nn.Module.__init__(self)
+        self.input_dim = inp_dim
+        self.hidden_size = int(_opt(options, "hidden_size"))
+        self.num_layers = int(_opt(options, "num_layers"))
+        self.bias = bool(strtobool(_opt(options, "bias")))
+        self.batch_first = bool(strtobool(_opt(options, "batch_first")))  # (the reference does not pass it on either)
+        self.dropout = float(_opt(options, "dropout"))
+        self.bidirectional = bool(strtobool(_opt(options, "bidirectional")))
+        name = type(self).__name__
+        if not 0.0 <= self.dropout < 1.0:
+            raise PkError("%s: dropout = %r must lie in [0, 1): at 1 every inter-layer activation is dropped and the scale "
+                          "1 / (1 - p) is infinite" % (name, self.dropout))
+        if self.hidden_size < 1 or self.num_layers < 1:
+            raise PkError("%s: hidden_size and num_layers must be positive" % name)
+        self._ndir = 2 if self.bidirectional else 1
+        n = self.num_layers * self._ndir
+        # what _Recurrent._layer reads: one entry per (layer, direction), each a unidirectional layer of its own
+        self._gates = [(None, None, None)] * len(F_.GATE_PERM[self.KIND])
+        self._lay, self._act = [self.hidden_size] * n, [act] * n
+        self._use_bn = self._use_ln = [0] * n
+        self.bidir = 0
+        setattr(self, self.ATTR, nn.ModuleList([_TorchRnnParams(len(self._gates), inp_dim, self.hidden_size, self.num_layers,
+                                                                self.bias, self.bidirectional)]))
+        self.out_dim = self.hidden_size + self.bidirectional * self.hidden_size
+
+    def _params(self):
+        return getattr(self, self.ATTR)[0]
+
+    def pk_unused_parameters(self):
+        return []
+
+    def pk_flat_groups(self):
+        """optim.FlatParams layout: per layer and direction the input matrix, the recurrent matrix, the two biases (back
+        to back: functional.adjacent_view gives them as one [2, G*H] block)."""
+        out = []
+        for k in range(self.num_layers):
+            for d in range(self._ndir):
+                w_ih, w_hh, b_ih, b_hh = self._params().of(k, d)
+                out += [[w_ih], [w_hh], [b for b in (b_ih, b_hh) if b is not None]]
+        return out
+
+    def _draw_masks(self, T, B, device):
+        """torch's dropout between layers: a fresh Bernoulli(1 - p) draw per element of every layer's output but the last,
+        in training mode only (it follows self.training, not to_do) - all num_layers - 1 masks as ONE draw on the device
+        generator, [L - 1, T, B, dirs * H]; None when nothing is dropped."""
+        if not self.training or self.dropout <= 0.0 or self.num_layers < 2:
+            return None
+        return torch.empty(self.num_layers - 1, T, B, self._ndir * self.hidden_size, device=device).bernoulli_(1.0 - self.dropout)
+
+    def _layer_params(self, i):
+        w_ih, w_hh, b_ih, b_hh = self._params().of(i // self._ndir, i % self._ndir)
+        perm = F_.GATE_PERM[self.KIND]
+        if len(perm) == 1:  # one gate: the matrices as they are, the kernel for the bias sum alone
+            bcat = F_.gates_pack(None, None, b_ih, b_hh, perm)[2] if self.bias else None
+            return [w_ih], [w_hh], bcat
+        Wcat, Ucat, bcat = F_.gates_pack(w_ih, w_hh, b_ih, b_hh, perm)
+        return [Wcat], [Ucat], bcat
+
+    def _layer_matrices(self, wps, ups, perf, edge):
+        return wps[0], ups[0], False, False
+
+    def forward(self, x, drop_masks=None):
+        if not x.is_cuda:
+            raise PkError("pytorch-kaldi_amd.nn.%s runs on the GPU only: set use_cuda=True" % type(self).__name__)
+        T, B, _ = x.shape
+        L, ndir, H = self.num_layers, self._ndir, self.hidden_size
+        masks, scale = None, 1.0
+        if self.training and self.dropout > 0.0 and L > 1:
+            scale = float(np.float32(1.0 / (1.0 - self.dropout)))  # rounded to fp32 once, here
+            if drop_masks is not None:  # injected (parity tests)
+                masks = [m.to(x.device).float().contiguous() for m in drop_masks]
+            else:
+                masks = self._draw_masks(T, B, x.device)
+        route = F_.rec_route(self.KIND, H, False, False, self.training)
+        inp_f = x
+        inp_b = F_.seq_join(x, want_y=False, want_rev=True)[1] if ndir == 2 else None
+        for k in range(L):
+            last = k == L - 1
+            yf = self._layer(k * ndir, inp_f, None, None, None, 1.0, route, True)[0]
+            yb = self._layer(k * ndir + 1, inp_b, None, None, None, 1.0, route, True)[0] if ndir == 2 else None
+            m = masks[k] if (masks is not None and not last) else None
+            if ndir == 1 and m is None:
+                inp_f = yf
+                continue
+            inp_f, inp_b = F_.seq_join(yf, yb, m, scale if m is not None else 1.0, True, ndir == 2 and not last)
+        return inp_f
+
+
+class LSTM_cudnn(_Cudnn):
+    """neural_networks.py:153-203.  c = f c + i g, h = o tanh(c) is the engine's LSTM cell with mask 1 and tanh; torch packs
+    the gates i, f, g, o, the kernels take f, i, o, c.  Initialisation as in the reference: torch's uniform draws, then
+    orthogonal_ on every weight_hh only when batch_first is true (the reference's condition, kept), zeros on the biases."""
+    KIND, ATTR = "LSTM", "lstm"
+
+    def __init__(self, options, inp_dim):
+        self._setup(options, inp_dim, "tanh")
+        for name, param in self.lstm[0].named_parameters():
+            if "weight_hh" in name:
+                if self.batch_first:
+                    nn.init.orthogonal_(param)
+            elif "bias" in name:
+                nn.init.zeros_(param)
+
+
+class RNN_cudnn(_Cudnn):
+    """neural_networks.py:256-297.  h = act(W x + b_ih + U h + b_hh) is the engine's RNN cell with mask 1."""
+    KIND, ATTR = "RNN", "rnn"
+
+    def __init__(self, options, inp_dim):
+        act = str(_opt(options, "nonlinearity"))
+        if act not in ("tanh", "relu"):
+            raise PkError("RNN_cudnn: nonlinearity %r (torch.nn.RNN takes 'tanh' or 'relu')" % (act,))
+        self._setup(options, inp_dim, act)
+        self.nonlinearity = act
+
+
+class GRU_cudnn(nn.Module):
+    """neural_networks.py:206-253.  Not on the engine: see the message."""
+
+    def __init__(self, options, inp_dim):
+        raise PkError("GRU_cudnn: torch.nn.GRU computes its candidate as n = tanh(W_n x + b_in + r * (U_n h + b_hn)) - the "
+                      "reset gate multiplies the recurrent product - which is none of the engine's cells: its GRU cell is the "
+                      "reference-form one, tanh(W x + U (r * h)).  Use arch_class = GRU, the class the engine runs.")
 
 
 class SincConv(nn.Module):
