@@ -235,12 +235,13 @@ int pk_logsoftmax_fwd_ld(void* stream, const float* x, int64_t ldx, int64_t rows
 /* Perf mode, Linear -> LogSoftmax heads (neural_networks.py:139-148 with dnn_act = softmax; the cost the reference
  * back-propagates through it: utils.py:2361): dz = dy - exp(y) * rowsum(dy) written once as the bf16 operand of the
  * dX / dW GEMMs (pitch ldb elements, a multiple of 8, pad columns zero) together with its fp32 column sums (the
- * bias gradient).  N <= 2048.  partial: pk_logsoftmax_bwd_bf16_partial_floats(rows, N) floats of workspace. */
+ * bias gradient).  N <= 8192 and ldb <= 8192 (rows of up to 2048 columns: a wave per row; longer ones: a 256-thread
+ * workgroup per row).  partial: pk_logsoftmax_bwd_bf16_partial_floats(rows, N) floats of workspace. */
 int64_t pk_logsoftmax_bwd_bf16_partial_floats(int64_t rows, int64_t N);
 int pk_logsoftmax_bwd_bf16(void* stream, const float* dy, const float* y, int64_t rows, int64_t N, uint16_t* dxb,
                            int64_t ldb, float* partial, float* colsum);
 /* The cost lines on such a head (utils.py:2361-2367: loss = NLLLoss()(out, lab), err = mean(argmax(out, 1) != lab))
- * in one pass over the log-posteriors y [rows][N], N <= 2048, labels int64 on the device.
+ * in one pass over the log-posteriors y [rows][N], N <= 8192, labels int64 on the device.
  * out4 (device) = { mean of -y[r][lab[r]] over the rows whose label is not ignore_index, error rate over all rows,
  * number of counted rows, number of labels outside [0, N) (the caller raises on it) }.
  * partial: pk_nll_err_partial_floats(rows) floats.  * loss_out (NULL or one float): a second copy of out4[0]; bad_acc (NULL or one float): += out4[3] in place. */
@@ -249,7 +250,7 @@ int pk_nll_err_fwd(void* stream, const float* y, const int64_t* lab, int64_t ign
                    float* partial, float* out4, float* loss_out, float* bad_acc);
 /* The same output together with the arg-max position of every row (first index on ties; a NaN row: column 0), and the
  * cost of such an output: cost_nll / cost_err (utils.py:2361-2367) as ONE gathered load and one compare per row instead of
- * a second pass over the [rows][N] log-posteriors.  amax: [rows] int32.  N <= 2048. */
+ * a second pass over the [rows][N] log-posteriors.  amax: [rows] int32.  N <= 8192. */
 int pk_logsoftmax_fwd_ld_argmax(void* stream, const float* x, int64_t ldx, int64_t rows, int64_t N, float* y, int32_t* amax);
 int pk_nll_err_fwd_argmax(void* stream, const float* y, const int64_t* lab, const int32_t* amax, int64_t ignore_index,
                           int64_t rows, int64_t N, float* partial, float* out4, float* loss_out, float* bad_acc);

@@ -1056,6 +1056,246 @@ __global__ __launch_bounds__(256) void nll_err_final_kernel(const float* __restr
     }
 }
 
+// ---- Block-per-row variants of the head kernels, for rows of 2049 .. 8192 columns ---------------------------------
+// (every Librispeech recipe has ~3400 senones).  The wave kernels stop at 64 lanes x 32 registers; here a 256-thread
+// workgroup owns a row and a thread holds up to NPT of its values: every element is still read from HBM once, all loads
+// of a thread are in flight together, and the reductions are wave shuffles plus one exchange of four values through
+// LDS.  Value i of thread t is column lsmb_col(i, t): with VEC (N a multiple of 4 and 16-byte aligned rows) the thread
+// owns 4-column chunks, chunk j at column (j * 256 + t) * 4 - 16-byte loads, 8-byte bf16 stores, and a chunk lies
+// entirely inside [0, N), [N, ldb) or beyond; without, single columns i * 256 + t.  Per-element expressions are the
+// wave kernels' (the ONEHOT dz, which no cross-lane sum enters, comes out with the same bits).
+template <bool VEC>
+__device__ __forceinline__ long lsmb_col(int i, int t) {
+    return VEC ? (long)((i >> 2) * 256 + t) * 4 + (i & 3) : (long)i * 256 + t;
+}
+template <int NPT, bool VEC>
+__device__ __forceinline__ void lsmb_load(const float* __restrict__ row, long N, int t, float pad, float (&v)[NPT]) {
+    if (VEC) {
+#pragma unroll
+        for (int j = 0; j < NPT / 4; ++j) {
+            const long c = (long)(j * 256 + t) * 4;
+            f32x4 q = {pad, pad, pad, pad};
+            if (c < N) q = *(const f32x4*)(row + c);
+            v[4 * j] = q[0], v[4 * j + 1] = q[1], v[4 * j + 2] = q[2], v[4 * j + 3] = q[3];
+        }
+    } else {
+#pragma unroll
+        for (int i = 0; i < NPT; ++i) {
+            const long c = (long)i * 256 + t;
+            v[i] = c < N ? row[c] : pad;
+        }
+    }
+}
+// sh: four floats; the caller keeps two uses of the same four apart by a barrier
+__device__ __forceinline__ float lsmb_block_max(float v, float* sh) {
+    v = pk_wave_max(v);
+    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return fmaxf(fmaxf(sh[0], sh[1]), fmaxf(sh[2], sh[3]));
+}
+__device__ __forceinline__ float lsmb_block_sum(float v, float* sh) {
+    v = pk_wave_sum(v);
+    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return (sh[0] + sh[1]) + (sh[2] + sh[3]);
+}
+
+// contract of logsoftmax_fwd_wave_kernel (input at pitch ldx, its pad columns never read; output at pitch N; LSM_FAR;
+// amax by the rule of nll_err_partial_kernel)
+template <int NPT, bool VEC>
+__global__ __launch_bounds__(256) void logsoftmax_fwd_block_kernel(const float* __restrict__ x, long ldx, long rows, long N,
+                                                                    float* __restrict__ y, int* __restrict__ amax) {
+    __shared__ float shm[4], shs[4], shb[4];
+    __shared__ long shi[4];
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    for (long r = blockIdx.x; r < rows; r += gridDim.x) {
+        float* yr = y + r * N;
+        float v[NPT];
+        lsmb_load<NPT, VEC>(x + r * ldx, N, t, -INFINITY, v);
+        float m = -INFINITY;
+#pragma unroll
+        for (int i = 0; i < NPT; ++i) m = fmaxf(m, v[i]);
+        m = lsmb_block_max(m, shm);
+        float sum = 0.f;
+#pragma unroll
+        for (int i = 0; i < NPT; ++i) sum += expf(v[i] - m);  // exp(-inf) = 0 for the padding
+        sum = lsmb_block_sum(sum, shs);  // (shm is written again behind this barrier, shs behind the next row's first)
+        const float ls = logf(sum), lse = m + ls;
+        const bool far = fabsf(m) > LSM_FAR;  // (see LSM_FAR)
+#pragma unroll
+        for (int i = 0; i < NPT; ++i) v[i] = far ? (v[i] - m) - ls : v[i] - lse;
+        if (VEC) {
+#pragma unroll
+            for (int j = 0; j < NPT / 4; ++j) {
+                const long c = (long)(j * 256 + t) * 4;
+                const f32x4 q = {v[4 * j], v[4 * j + 1], v[4 * j + 2], v[4 * j + 3]};
+                if (c < N) *(f32x4*)(yr + c) = q;
+            }
+        } else {
+#pragma unroll
+            for (int i = 0; i < NPT; ++i) {
+                const long c = (long)i * 256 + t;
+                if (c < N) yr[c] = v[i];
+            }
+        }
+        if (amax != nullptr) {
+            // thread 0 visits column 0 first and keeps it on a NaN row, through both merges
+            float best = -INFINITY;
+            long besti = N;
+#pragma unroll
+            for (int i = 0; i < NPT; ++i) {
+                const long c = lsmb_col<VEC>(i, t);
+                const float u = c < N ? v[i] : -INFINITY;
+                if (c < N && (u > best || (u == best && c < besti) || besti == N)) best = u, besti = c;
+            }
+#pragma unroll
+            for (int off = 32; off > 0; off >>= 1) {
+                const float ob = __shfl_xor(best, off);
+                const long oi = __shfl_xor(besti, off);
+                if (ob > best || (ob == best && oi < besti)) best = ob, besti = oi;
+            }
+            if (lane == 0) shb[wave] = best, shi[wave] = besti;
+            __syncthreads();
+            if (t == 0) {
+#pragma unroll
+                for (int w = 1; w < 4; ++w) {
+                    const float ob = shb[w];
+                    const long oi = shi[w];
+                    if (ob > best || (ob == best && oi < besti)) best = ob, besti = oi;
+                }
+                amax[r] = (int)besti;
+            }
+            // (shb / shi are written again behind two more barriers, which thread 0 reaches after this read)
+        }
+    }
+}
+
+// contract of logsoftmax_bwd_bf16_kernel.  The block walks rows blockIdx.x, + gridDim.x, ...; a column has ONE owner per
+// block, whose register carries its sum over those rows: the partial row needs no merge.
+template <int NPT, bool VEC, bool ONEHOT>
+__global__ __launch_bounds__(256) void logsoftmax_bwd_bf16_block_kernel(const float* __restrict__ dy, const float* __restrict__ y,
+                                                                         const long* __restrict__ lab,
+                                                                         const float* __restrict__ dloss,
+                                                                         const float* __restrict__ count, long ignore_index,
+                                                                         long rows, long N, unsigned short* __restrict__ dxb,
+                                                                         long ldb, long pitch, float* __restrict__ partial) {
+    __shared__ float shs[2][4];  // by row parity: one barrier per row
+    const int t = threadIdx.x;
+    float scale = 0.f;
+    if (ONEHOT) {
+        const float cnt = count[0];
+        scale = cnt > 0.f ? dloss[0] / cnt : 0.f;
+    }
+    float acc[NPT];
+#pragma unroll
+    for (int i = 0; i < NPT; ++i) acc[i] = 0.f;
+    int par = 0;
+    for (long r = blockIdx.x; r < rows; r += gridDim.x, par ^= 1) {
+        unsigned short* o = dxb + r * pitch;
+        float g[NPT], e[NPT];
+        float sum = 0.f;
+        long lr = -1;
+        if (ONEHOT) {
+            lr = lab[r];
+            if (lr == ignore_index || lr < 0 || lr >= N) lr = -1;  // (an out-of-range label is counted by the forward pass)
+            sum = lr >= 0 ? -scale : 0.f;
+        }
+        lsmb_load<NPT, VEC>(y + r * N, N, t, -INFINITY, e);
+        if (ONEHOT) {
+#pragma unroll
+            for (int i = 0; i < NPT; ++i) g[i] = lsmb_col<VEC>(i, t) == lr ? -scale : 0.f;
+        } else {
+            lsmb_load<NPT, VEC>(dy + r * N, N, t, 0.f, g);
+#pragma unroll
+            for (int i = 0; i < NPT; ++i) sum += g[i];
+            sum = lsmb_block_sum(sum, shs[par]);
+        }
+        float d[NPT];
+#pragma unroll
+        for (int i = 0; i < NPT; ++i) {
+            const long c = lsmb_col<VEC>(i, t);
+            d[i] = c < N ? g[i] - expf(e[i]) * sum : 0.f;
+            acc[i] += d[i];
+        }
+        if (VEC) {
+#pragma unroll
+            for (int j = 0; j < NPT / 4; ++j) {
+                const long c = (long)(j * 256 + t) * 4;
+                const uint2 q = {pk_pack_bf2(d[4 * j], d[4 * j + 1]), pk_pack_bf2(d[4 * j + 2], d[4 * j + 3])};
+                if (c < ldb) *(uint2*)(o + c) = q;
+            }
+        } else {
+#pragma unroll
+            for (int i = 0; i < NPT; ++i) {
+                const long c = (long)i * 256 + t;
+                if (c < ldb) o[c] = pk_f2bf(d[i]);
+            }
+        }
+    }
+    // one partial row per block, in the layout col_reduce_final_kernel reads
+#pragma unroll
+    for (int i = 0; i < NPT; ++i) {
+        const long c = lsmb_col<VEC>(i, t);
+        if (c < N) {
+            const pk_f32x2 q = {acc[i], 0.f};
+            *(pk_f32x2*)(partial + ((long)blockIdx.x * N + c) * 2) = q;
+        }
+    }
+}
+
+// nll_err_partial_kernel for such rows (the cost without the arg-max positions): partial [blocks][4], same decisions
+template <int NPT, bool VEC>
+__global__ __launch_bounds__(256) void nll_err_partial_block_kernel(const float* __restrict__ y, const long* __restrict__ lab,
+                                                                     long ignore_index, long rows, long N,
+                                                                     float* __restrict__ partial) {
+    __shared__ float shb[2][4], sha[2][4];  // by row parity: one barrier per row
+    __shared__ long shi[2][4];
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    float loss = 0.f, err = 0.f, cnt = 0.f, bad = 0.f;  // (thread 0's count)
+    int par = 0;
+    for (long r = blockIdx.x; r < rows; r += gridDim.x, par ^= 1) {
+        const long lr = lab[r];
+        const bool ignored = lr == ignore_index;
+        const bool in_range = lr >= 0 && lr < N;
+        float v[NPT];
+        lsmb_load<NPT, VEC>(y + r * N, N, t, -INFINITY, v);
+        float best = -INFINITY, at_lab = 0.f;
+        long besti = N;
+#pragma unroll
+        for (int i = 0; i < NPT; ++i) {
+            const long c = lsmb_col<VEC>(i, t);
+            const float u = c < N ? v[i] : -INFINITY;
+            if (c < N && (u > best || (u == best && c < besti) || besti == N)) best = u, besti = c;  // NaN rows: index of the first column
+            if (c == lr) at_lab = u;
+        }
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) {
+            const float ob = __shfl_xor(best, off);
+            const long oi = __shfl_xor(besti, off);
+            if (ob > best || (ob == best && oi < besti)) best = ob, besti = oi;
+            at_lab += __shfl_xor(at_lab, off);
+        }
+        if (lane == 0) shb[par][wave] = best, shi[par][wave] = besti, sha[par][wave] = at_lab;
+        __syncthreads();
+        if (t == 0) {
+#pragma unroll
+            for (int w = 1; w < 4; ++w) {
+                const float ob = shb[par][w];
+                const long oi = shi[par][w];
+                if (ob > best || (ob == best && oi < besti)) best = ob, besti = oi;
+                at_lab += sha[par][w];
+            }
+            err += besti != lr ? 1.f : 0.f;
+            if (!ignored && in_range) loss -= at_lab, cnt += 1.f;
+            if (!ignored && !in_range) bad += 1.f;
+        }
+    }
+    if (t == 0) {
+        float* o = partial + (long)blockIdx.x * 4;
+        o[0] = loss, o[1] = err, o[2] = cnt, o[3] = bad;
+    }
+}
+
 inline int ew_blocks(long n) {
     long b = (n + 255) / 256;
     if (b > 4096) b = 4096;
@@ -1470,6 +1710,29 @@ extern "C" int pk_bn_stats_merge_finalize_gates(void* stream, const float* parti
         else hipLaunchKernelGGL((KERNEL<32>), wgrid, dim3(256), 0, st, __VA_ARGS__);                        \
     } while (0)
 
+// The block-per-row kernels: rows of 2049 .. 8192 columns - and, for A/B runs and the tests that compare the two families,
+// every row length when PK_EXPERIMENT has head_block=1 (read per call: a test flips it inside one process).
+constexpr int64_t LSM_WAVE_MAX = 2048, LSM_BLOCK_MAX = 8192;
+static inline bool lsm_block_rows(int64_t N) {
+    if (N > LSM_WAVE_MAX) return true;
+    const char* e = pk_experiment("head_block");
+    return e != nullptr && e[0] == '1';
+}
+static inline bool lsm_aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+// W: the columns a block must cover (N, or the padded width a backward writes); VEC: see lsmb_col
+#define PK_LSM_BLOCK_DISPATCH(W, VEC, LAUNCH)    \
+    do {                                          \
+        if (VEC) {                                \
+            if ((W) <= 2048) LAUNCH(8, true);     \
+            else if ((W) <= 4096) LAUNCH(16, true); \
+            else LAUNCH(32, true);                \
+        } else {                                  \
+            if ((W) <= 2048) LAUNCH(8, false);    \
+            else if ((W) <= 4096) LAUNCH(16, false); \
+            else LAUNCH(32, false);               \
+        }                                         \
+    } while (0)
+
 extern "C" int pk_logsoftmax_fwd_ld(void* stream, const float* x, int64_t ldx, int64_t rows, int64_t N, float* y) {
     if (rows == 0) return 0;
     PK_REQUIRE(ldx >= N, "pk_logsoftmax_fwd_ld: input pitch shorter than a row");
@@ -1488,10 +1751,20 @@ extern "C" int pk_logsoftmax_fwd_ld(void* stream, const float* x, int64_t ldx, i
 extern "C" int pk_logsoftmax_fwd_ld_argmax(void* stream, const float* x, int64_t ldx, int64_t rows, int64_t N, float* y,
                                            int32_t* amax) {
     if (rows == 0) return 0;
-    PK_REQUIRE(ldx >= N && N >= 1 && N <= 2048, "pk_logsoftmax_fwd_ld_argmax: rows of 1..2048 columns, pitch >= row length");
+    PK_REQUIRE(ldx >= N && N >= 1 && N <= LSM_BLOCK_MAX, "pk_logsoftmax_fwd_ld_argmax: rows of 1..8192 columns, pitch >= row length");
     PK_REQUIRE(x && y && amax, "pk_logsoftmax_fwd_ld_argmax: null argument");
     hipStream_t st = pk_stream(stream);
-    PK_LSM_DISPATCH(logsoftmax_fwd_wave_kernel, x, (long)ldx, (long)rows, (long)N, y, (int*)amax);
+    if (lsm_block_rows(N)) {
+        // a row per block and pass; ~8 resident blocks per CU, the rest of a large batch by the stride loop
+        const dim3 grid((unsigned)(rows < 2048 ? rows : 2048));
+        const bool vec = (N % 4) == 0 && (ldx % 4) == 0 && lsm_aligned16(x) && lsm_aligned16(y);
+#define PK_LSMF(NPT, VEC) \
+    hipLaunchKernelGGL((logsoftmax_fwd_block_kernel<NPT, VEC>), grid, dim3(256), 0, st, x, (long)ldx, (long)rows, (long)N, y, (int*)amax)
+        PK_LSM_BLOCK_DISPATCH(N, vec, PK_LSMF);
+#undef PK_LSMF
+    } else {
+        PK_LSM_DISPATCH(logsoftmax_fwd_wave_kernel, x, (long)ldx, (long)rows, (long)N, y, (int*)amax);
+    }
     PK_LAUNCH_CHECK();
     return 0;
 }
@@ -1515,15 +1788,36 @@ static inline long lsm_bf16_blocks(int64_t rows, int64_t N) {
     return b;
 }
 
-extern "C" int64_t pk_logsoftmax_bwd_bf16_partial_floats(int64_t rows, int64_t N) { return lsm_bf16_blocks(rows, N) * N * 2; }
+// ... of the block-per-row kernel: a block is as long-lived as it can be (its threads carry the column sums), and the
+// partial workspace is blocks x N x 2 floats: a row per block up to 1024 blocks (a batch of 128 frames: 128 workgroups
+// on 128 CUs), beyond that the stride loop - 64 000 x 3400: 63 rows per block, 28 MB of partials next to 435 MB of dz
+static inline long lsm_bf16_block_blocks(int64_t rows) { return rows < 1 ? 1 : rows < 1024 ? (long)rows : 1024; }
+
+extern "C" int64_t pk_logsoftmax_bwd_bf16_partial_floats(int64_t rows, int64_t N) {
+    return (lsm_block_rows(N) ? lsm_bf16_block_blocks(rows) : lsm_bf16_blocks(rows, N)) * N * 2;
+}
 
 static int lsm_bwd_bf16_launch(hipStream_t st, bool onehot, const float* dy, const float* y, const long* lab,
                                const float* dloss, const float* count, long ignore_index, int64_t rows, int64_t N,
                                uint16_t* dxb, int64_t ldb, float* partial, float* colsum, int64_t pitch = 0) {
     if (pitch <= 0) pitch = ldb;
-    const long blocks = lsm_bf16_blocks(rows, N);
+    const bool block = lsm_block_rows(N);
+    const long blocks = block ? lsm_bf16_block_blocks(rows) : lsm_bf16_blocks(rows, N);
     const dim3 grid((unsigned)blocks);
     unsigned short* o = (unsigned short*)dxb;
+    if (block) {
+        // (ldb and pitch are multiples of 8: with N a multiple of 4 every 4-column chunk of a row is 8-byte aligned in dz)
+        const bool vec = (N % 4) == 0 && lsm_aligned16(y) && (onehot || lsm_aligned16(dy)) && ((uintptr_t)dxb & 7) == 0;
+#define PK_LSMBB(NPT, VEC)                                                                                                     \
+    do {                                                                                                                       \
+        if (onehot) hipLaunchKernelGGL((logsoftmax_bwd_bf16_block_kernel<NPT, VEC, true>), grid, dim3(256), 0, st, dy, y, lab,  \
+                                       dloss, count, ignore_index, (long)rows, (long)N, o, (long)ldb, (long)pitch, partial);   \
+        else hipLaunchKernelGGL((logsoftmax_bwd_bf16_block_kernel<NPT, VEC, false>), grid, dim3(256), 0, st, dy, y, lab, dloss, \
+                                count, ignore_index, (long)rows, (long)N, o, (long)ldb, (long)pitch, partial);                 \
+    } while (0)
+        PK_LSM_BLOCK_DISPATCH(ldb, vec, PK_LSMBB);
+#undef PK_LSMBB
+    } else {
 #define PK_LSMB(NPL)                                                                                                      \
     do {                                                                                                                  \
         if (onehot) hipLaunchKernelGGL((logsoftmax_bwd_bf16_kernel<NPL, true>), grid, dim3(256), 0, st, dy, y, lab, dloss, \
@@ -1536,6 +1830,7 @@ static int lsm_bwd_bf16_launch(hipStream_t st, bool onehot, const float* dy, con
     else if (ldb <= 1024) PK_LSMB(16);
     else PK_LSMB(32);
 #undef PK_LSMB
+    }
     PK_LAUNCH_CHECK();
     hipLaunchKernelGGL(col_reduce_final_kernel, dim3((unsigned)((N + CF_COLS - 1) / CF_COLS)), dim3(CF_COLS * CF_GROUPS), 0, st,
                        partial, (int)blocks, (long)N, colsum, (float*)nullptr, (float*)nullptr, (float*)nullptr, (unsigned short*)nullptr, 0L, 0L, 0);
@@ -1546,8 +1841,8 @@ static int lsm_bwd_bf16_launch(hipStream_t st, bool onehot, const float* dy, con
 extern "C" int pk_logsoftmax_bwd_bf16(void* stream, const float* dy, const float* y, int64_t rows, int64_t N, uint16_t* dxb,
                                       int64_t ldb, float* partial, float* colsum) {
     if (rows == 0) return 0;
-    PK_REQUIRE(N >= 1 && N <= 2048, "pk_logsoftmax_bwd_bf16: rows of 1..2048 columns (longer rows: pk_logsoftmax_bwd + pk_cvt_bf16)");
-    PK_REQUIRE(ldb >= N && ldb <= 2048 && (ldb % 8) == 0, "pk_logsoftmax_bwd_bf16: bad bf16 pitch");
+    PK_REQUIRE(N >= 1 && N <= LSM_BLOCK_MAX, "pk_logsoftmax_bwd_bf16: rows of 1..8192 columns");
+    PK_REQUIRE(ldb >= N && ldb <= LSM_BLOCK_MAX && (ldb % 8) == 0, "pk_logsoftmax_bwd_bf16: bad bf16 pitch");
     PK_REQUIRE(partial && colsum, "pk_logsoftmax_bwd_bf16: null workspace");
     return lsm_bwd_bf16_launch(pk_stream(stream), false, dy, y, nullptr, nullptr, nullptr, 0, rows, N, dxb, ldb, partial, colsum);
 }
@@ -1556,8 +1851,8 @@ extern "C" int pk_nll_logsoftmax_bwd_bf16(void* stream, const float* y, const in
                                           const float* count, int64_t ignore_index, int64_t rows, int64_t N, uint16_t* dxb,
                                           int64_t ldb, float* partial, float* colsum) {
     if (rows == 0) return 0;
-    PK_REQUIRE(N >= 1 && N <= 2048, "pk_nll_logsoftmax_bwd_bf16: rows of 1..2048 columns");
-    PK_REQUIRE(ldb >= N && ldb <= 2048 && (ldb % 8) == 0, "pk_nll_logsoftmax_bwd_bf16: bad bf16 pitch");
+    PK_REQUIRE(N >= 1 && N <= LSM_BLOCK_MAX, "pk_nll_logsoftmax_bwd_bf16: rows of 1..8192 columns");
+    PK_REQUIRE(ldb >= N && ldb <= LSM_BLOCK_MAX && (ldb % 8) == 0, "pk_nll_logsoftmax_bwd_bf16: bad bf16 pitch");
     PK_REQUIRE(y && lab && dloss && count && partial && colsum, "pk_nll_logsoftmax_bwd_bf16: null argument");
     return lsm_bwd_bf16_launch(pk_stream(stream), true, nullptr, y, (const long*)lab, dloss, count, (long)ignore_index, rows, N,
                                dxb, ldb, partial, colsum);
@@ -1568,8 +1863,8 @@ extern "C" int pk_nll_logsoftmax_bwd_bf16(void* stream, const float* y, const in
 extern "C" int pk_logsoftmax_bwd_bf16_p(void* stream, const float* dy, const float* y, int64_t rows, int64_t N, uint16_t* dxb,
                                         int64_t ldb, int64_t pitch, float* partial, float* colsum) {
     if (rows == 0) return 0;
-    PK_REQUIRE(N >= 1 && N <= 2048, "pk_logsoftmax_bwd_bf16_p: rows of 1..2048 columns");
-    PK_REQUIRE(ldb >= N && ldb <= 2048 && (ldb % 8) == 0 && pitch >= ldb && (pitch % 8) == 0, "pk_logsoftmax_bwd_bf16_p: bad bf16 pitch");
+    PK_REQUIRE(N >= 1 && N <= LSM_BLOCK_MAX, "pk_logsoftmax_bwd_bf16_p: rows of 1..8192 columns");
+    PK_REQUIRE(ldb >= N && ldb <= LSM_BLOCK_MAX && (ldb % 8) == 0 && pitch >= ldb && (pitch % 8) == 0, "pk_logsoftmax_bwd_bf16_p: bad bf16 pitch");
     PK_REQUIRE(partial && colsum, "pk_logsoftmax_bwd_bf16_p: null workspace");
     return lsm_bwd_bf16_launch(pk_stream(stream), false, dy, y, nullptr, nullptr, nullptr, 0, rows, N, dxb, ldb, partial, colsum, pitch);
 }
@@ -1577,8 +1872,8 @@ extern "C" int pk_nll_logsoftmax_bwd_bf16_p(void* stream, const float* y, const 
                                             const float* count, int64_t ignore_index, int64_t rows, int64_t N, uint16_t* dxb,
                                             int64_t ldb, int64_t pitch, float* partial, float* colsum) {
     if (rows == 0) return 0;
-    PK_REQUIRE(N >= 1 && N <= 2048, "pk_nll_logsoftmax_bwd_bf16_p: rows of 1..2048 columns");
-    PK_REQUIRE(ldb >= N && ldb <= 2048 && (ldb % 8) == 0 && pitch >= ldb && (pitch % 8) == 0, "pk_nll_logsoftmax_bwd_bf16_p: bad bf16 pitch");
+    PK_REQUIRE(N >= 1 && N <= LSM_BLOCK_MAX, "pk_nll_logsoftmax_bwd_bf16_p: rows of 1..8192 columns");
+    PK_REQUIRE(ldb >= N && ldb <= LSM_BLOCK_MAX && (ldb % 8) == 0 && pitch >= ldb && (pitch % 8) == 0, "pk_nll_logsoftmax_bwd_bf16_p: bad bf16 pitch");
     PK_REQUIRE(y && lab && dloss && count && partial && colsum, "pk_nll_logsoftmax_bwd_bf16_p: null argument");
     return lsm_bwd_bf16_launch(pk_stream(stream), true, nullptr, y, (const long*)lab, dloss, count, (long)ignore_index, rows, N,
                                dxb, ldb, partial, colsum, pitch);
@@ -1596,12 +1891,26 @@ extern "C" int64_t pk_nll_err_partial_floats(int64_t rows) { return nll_err_bloc
 
 extern "C" int pk_nll_err_fwd(void* stream, const float* y, const int64_t* lab, int64_t ignore_index, int64_t rows, int64_t N,
                               float* partial, float* out4, float* loss_out, float* bad_acc) {
-    PK_REQUIRE(rows > 0 && N >= 1 && N <= 2048, "pk_nll_err_fwd: needs rows of 1..2048 columns");
+    PK_REQUIRE(rows > 0 && N >= 1 && N <= LSM_BLOCK_MAX, "pk_nll_err_fwd: needs rows of 1..8192 columns");
     PK_REQUIRE(y && lab && partial && out4, "pk_nll_err_fwd: null argument");
     hipStream_t st = pk_stream(stream);
     const long blocks = nll_err_blocks(rows);
-    const dim3 grid((unsigned)blocks);
     const long* l = (const long*)lab;
+    if (lsm_block_rows(N)) {
+        // one partial entry per BLOCK: at most as many blocks as the workspace has entries for waves
+        const long bb = rows < blocks * 4 ? (long)rows : blocks * 4;
+        const dim3 bgrid((unsigned)bb);
+        const bool vec = (N % 4) == 0 && lsm_aligned16(y);
+#define PK_NLLB(NPT, VEC) \
+    hipLaunchKernelGGL((nll_err_partial_block_kernel<NPT, VEC>), bgrid, dim3(256), 0, st, y, l, (long)ignore_index, (long)rows, (long)N, partial)
+        PK_LSM_BLOCK_DISPATCH(N, vec, PK_NLLB);
+#undef PK_NLLB
+        PK_LAUNCH_CHECK();
+        hipLaunchKernelGGL(nll_err_final_kernel, dim3(1), dim3(256), 0, st, partial, bb, (long)rows, out4, loss_out, bad_acc);
+        PK_LAUNCH_CHECK();
+        return 0;
+    }
+    const dim3 grid((unsigned)blocks);
     if (N <= 64) hipLaunchKernelGGL((nll_err_partial_kernel<1>), grid, dim3(256), 0, st, y, l, (long)ignore_index, (long)rows, (long)N, partial);
     else if (N <= 256) hipLaunchKernelGGL((nll_err_partial_kernel<4>), grid, dim3(256), 0, st, y, l, (long)ignore_index, (long)rows, (long)N, partial);
     else if (N <= 1024) hipLaunchKernelGGL((nll_err_partial_kernel<16>), grid, dim3(256), 0, st, y, l, (long)ignore_index, (long)rows, (long)N, partial);
