@@ -506,6 +506,31 @@ int pk_seq_join_fwd(void* stream, const float* yf, const float* yb, const float*
 int pk_seq_join_bwd(void* stream, const float* dy, const float* dy_rev, const float* mask, float scale, int64_t T, int64_t B,
                     int64_t H, int ndir, float* dyf, float* dyb);
 
+/* ---- length-aware decoding batches (pk_seqlen.hip): B sentences of lengths lens[b] (int32 in DEVICE memory, [B],
+ * 1 <= lens[b] <= T), zero-padded at the END.  The reference's bidirectional layers run cat([x, flip(x)], dim=1) on one
+ * sentence (neural_networks.py:1083-1085 and its siblings); in a padded batch the reversal is per sentence, so that the
+ * backward direction of a short sentence starts at ITS last frame, not inside the padding.  With L = lens[b]:
+ *   pk_seq_pack_len   x [T][B][D], dense:
+ *                         out_f[t][b][:] = t < L ? x[t][b][:]     : 0
+ *                         out_r[t][b][:] = t < L ? x[L-1-t][b][:] : 0
+ *                     ldo = floats between consecutive t of either output (>= B*D).  out_r = out_f + B*D with
+ *                     ldo = 2*B*D writes [T][2B][D], the reference's cat, directly.  One output may be NULL, not both.
+ *   pk_seq_join_len   hf, hb [T][B][H] at a pitch of ldi floats per step (>= B*H): the halves of one [T][2B][H] tensor or
+ *                     two tensors; hb in the per-sentence REVERSED order (what a layer gives on out_r):
+ *                         y_f[t][b][0:H]  = t < L ? hf[t][b][:]     : 0
+ *                         y_f[t][b][H:2H] = t < L ? hb[L-1-t][b][:] : 0
+ *                         y_r[t][b][:]    = t < L ? y_f[L-1-t][b][:] : 0     the next layer's reversed input, same read
+ *                     both at a pitch of ldo floats per step (>= 2*B*H).  One of y_f / y_r may be NULL, not both.
+ * T, B, D, H >= 1.  Forward only.  One launch each; per input element 4 bytes read and 4 written for every output asked
+ * for (pk_seq_pack_len reads an element a second time for out_r), plus 4 bytes of lens per unit.  16-byte accesses when the
+ * width and the pitches are multiples of 4 and every pointer is 16-byte aligned, scalar ones otherwise.  A length outside
+ * 0 .. T is clamped into that range by the kernels: whatever lens holds, no index leaves the tensors.  Bad arguments - a
+ * required pointer NULL, a size below 1, both outputs NULL, a pitch smaller than a step - return 2 and launch nothing. */
+int pk_seq_pack_len(void* stream, const float* x, const int32_t* lens, int64_t T, int64_t B, int64_t D, float* out_f,
+                    float* out_r, int64_t ldo);
+int pk_seq_join_len(void* stream, const float* hf, const float* hb, int64_t ldi, const int32_t* lens, int64_t T, int64_t B,
+                    int64_t H, float* y_f, float* y_r, int64_t ldo);
+
 /* persistent-recurrence health: number of spin time-outs since the last reset
  * (host-mapped counter, readable without a device sync). */
 unsigned pk_persist_error_count(void);

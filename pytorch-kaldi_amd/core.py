@@ -74,6 +74,35 @@ def sentence_lengths(data_end_index):
     return np.diff(end, prepend=0)
 
 
+def forward_batch():
+    """PK_FORWARD_BATCH = n: a `to_do = forward` chunk goes through the engine n sentences at a time (1, the default: one
+    by one, the reference's loop)."""
+    raw = os.environ.get("PK_FORWARD_BATCH", "1")
+    try:
+        n = int(raw)
+    except ValueError:
+        n = 0
+    if n < 1:
+        raise RuntimeError("PK_FORWARD_BATCH = %r: a positive number of sentences per forward batch" % (raw,))
+    return n
+
+
+def forward_groups(lengths, n):
+    """Consecutive sentences n at a time, in data order, the last group smaller: [(first, past-the-last, longest)]."""
+    lengths = [int(v) for v in lengths]
+    if n < 1:
+        raise ValueError("forward_groups: n = %r sentences per group" % (n,))
+    return [(s, min(s + n, len(lengths)), max(lengths[s:s + n])) for s in range(0, len(lengths), n)]
+
+
+def padded_rows(lengths, max_len):
+    """Rows of the end-padded (max_len, B) batch that hold frames, as indices t * B + b into its flattened rows, sentence
+    after sentence: rows[i] is where frame i of the group's concatenated sentences goes, and where its output is found."""
+    B = len(lengths)
+    assert all(1 <= int(n) <= max_len for n in lengths), (list(lengths), max_len)
+    return np.concatenate([np.arange(int(n), dtype=np.int64) * B + b for b, n in enumerate(lengths)])
+
+
 class BatchAssembler:
     """Zero-padded (max_len, B, D) batches with a random number of leading zeros per sentence
     (core.py:581-598), built with one gather from the chunk instead of B slice copies.  The chunk gets one
@@ -364,6 +393,45 @@ def run_nn_dp(data_name, data_set, data_end_index, fea_dict, lab_dict, arch_dict
     err_sum = torch.zeros((), device=device)
     snt_index, beg_snt = 0, 0
     fence = F_.StepFence()  # eager steps: at most PK_STEPS_IN_FLIGHT of them enqueued ahead of the GPU
+
+    def forward_batched(n):
+        # PK_FORWARD_BATCH = n > 1: n consecutive sentences per forward_model call.  A sequence model takes them as ONE
+        # end-padded (max_len, nb, .) batch under functional.sentence_lengths (left offset 0, `random` is not consumed);
+        # anything else takes their frames back to back.  The frames of the group's outputs come back in ONE
+        # device-to-host copy and are written sentence by sentence, as the loop below writes them.
+        lens_all = sentence_lengths(end)
+        for s, e, max_len in forward_groups(lens_all, n):
+            lens, nb = [int(v) for v in lens_all[s:e]], e - s
+            frames = data_set[int(end[s]) - lens[0]:int(end[e - 1]), :].to(device)
+            if seq_model:
+                rows = torch.from_numpy(padded_rows(lens, max_len)).to(device)
+                inp = torch.zeros(max_len * nb, frames.shape[1], device=device).index_copy_(0, rows, frames)
+                with torch.no_grad(), F_.sentence_lengths(lens):
+                    outs_dict = forward_model(fea_dict, lab_dict, arch_dict, model, nns, costs, inp.view(max_len, nb, -1),
+                                              inp_out_dict, max_len, nb, to_do, forward_outs)
+                outs = [outs_dict[name].detach().reshape(max_len * nb, -1).index_select(0, rows) for name in forward_outs]
+            else:
+                with torch.no_grad():
+                    outs_dict = forward_model(fea_dict, lab_dict, arch_dict, model, nns, costs, frames.contiguous(),
+                                              inp_out_dict, 0, 1, to_do, forward_outs)
+                outs = [outs_dict[name].detach() for name in forward_outs]
+            widths = np.cumsum([0] + [o.shape[1] for o in outs])
+            host = (outs[0] if len(outs) == 1 else torch.cat(outs, 1)).cpu().numpy()
+            beg = 0
+            for k in range(nb):
+                for out_id, name in enumerate(forward_outs):
+                    out_save = host[beg:beg + lens[k], widths[out_id]:widths[out_id + 1]]
+                    if forward_normalize_post[out_id]:
+                        c = counts[out_id]
+                        out_save = out_save - np.log(c / np.sum(c))
+                    write_mat(post_file[name], out_save, data_name[s + k])
+                beg += lens[k]
+
+    n_forward = forward_batch() if to_do == "forward" else 1
+    if n_forward > 1:
+        if rank == 0:
+            forward_batched(n_forward)
+        N_batches = 0  # (the sentence-by-sentence loop below has nothing left to do)
     for i in range(N_batches):
         max_len = 0
         if to_do == "forward":

@@ -1650,6 +1650,121 @@ def seq_join(yf, yb=None, mask=None, scale=1.0, want_y=True, want_rev=False):
     return SeqJoinFn.apply(yf, yb, mask, scale, want_y, want_rev)
 
 
+# ----------------------------------------------------------------------------
+# Length-aware decoding batches (csrc/pk_seqlen.hip): B sentences of different lengths in one zero-padded [T, B, .]
+# batch, padding at the END.  Under `with sentence_lengths(lens):` the bidirectional recurrent classes of nn.py reverse
+# every sentence on its own, so that its rows equal what the sentence gives alone.  Forward only.
+# ----------------------------------------------------------------------------
+class sentence_lengths:
+    """Context manager: the sentences of every [T, B, .] batch handed to a recurrent class inside the block have the
+    lengths `lens` (B integers in 1 .. T) and zeros behind them.  Holds the host tuple and, from the first use on, an
+    int32 tensor on the device; blocks nest, and the lengths of the enclosing block are back in force on exit."""
+
+    _active = None
+
+    def __init__(self, lens):
+        self.lens = tuple(int(n) for n in lens)
+        self._dev = None
+        self._prev = []
+
+    def __enter__(self):
+        self._prev.append(sentence_lengths._active)
+        sentence_lengths._active = self
+        return self
+
+    def __exit__(self, *exc):
+        sentence_lengths._active = self._prev.pop()
+        return False
+
+    def device_tensor(self, device):
+        if self._dev is None or self._dev.device != device:
+            self._dev = torch.tensor(self.lens, dtype=torch.int32, device=device)
+        return self._dev
+
+    def check(self, who, x):
+        """Host-side checks of a [T, B, .] input against the lengths, before anything is launched."""
+        T, B = int(x.shape[0]), int(x.shape[1])
+        if len(self.lens) != B:
+            raise _lib.PkError("%s: %d sentence lengths for a batch of %d sentences" % (who, len(self.lens), B))
+        bad = [n for n in self.lens if n < 1 or n > T]
+        if bad:
+            raise _lib.PkError("%s: sentence lengths must lie in 1 .. T = %d (got %s)" % (who, T, bad[:8]))
+        if torch.is_grad_enabled() and x.requires_grad:
+            raise _lib.PkError("%s: length-aware batches are forward only (the input requires grad and autograd is on)" % who)
+
+
+def current_lengths():
+    """The sentence_lengths block in force, or None."""
+    return sentence_lengths._active
+
+
+def _lens_arg(who, lens, x):
+    lens = current_lengths() if lens is None else lens
+    if lens is None:
+        raise _lib.PkError("%s: no sentence lengths (pass them, or call inside `with sentence_lengths(...)`)" % who)
+    if not isinstance(lens, sentence_lengths):
+        lens = sentence_lengths(lens)
+    _need_gpu(x)
+    lens.check(who, x)
+    return lens
+
+
+def seq_pack_len(x, lens=None, want_f=True, want_r=True, cat=False):
+    """x [T, B, D], zero-padded behind each sentence -> (out_f, out_r): x with its padding rows zeroed, and every sentence
+    reversed in time on its own, out_r[t][b] = x[L_b-1-t][b] (pk_seq_pack_len, one launch).  An output not asked for is
+    None.  cat = True: ONE tensor [T, 2B, D] = cat([out_f, out_r], dim=1), written in place - the rows a shared-weight
+    bidirectional layer runs as a unidirectional one.  lens: a sentence_lengths, a sequence, or None = the block in force."""
+    lens = _lens_arg("seq_pack_len", lens, x)
+    T, B, D = x.shape
+    x = x.detach().contiguous()
+    if cat:
+        full = _new(T, 2 * B, D, like=x)
+        out_f, out_r, ldo = full[:, :B], full[:, B:], 2 * B * D
+    else:
+        if not (want_f or want_r):
+            raise _lib.PkError("seq_pack_len: neither output is asked for")
+        out_f = _new(T, B, D, like=x) if want_f else None
+        out_r = _new(T, B, D, like=x) if want_r else None
+        ldo = B * D
+    _lib.check(_lib.load().pk_seq_pack_len(_stream(), _p(x), _p(lens.device_tensor(x.device)), T, B, D, _p(out_f), _p(out_r),
+                                           ldo), "pk_seq_pack_len")
+    return full if cat else (out_f, out_r)
+
+
+def seq_join_len(hf, hb=None, lens=None, want_y=True, want_rev=False, cat=False):
+    """The two directions of a layer joined along the features, the backward one turned round sentence by sentence:
+    y[t][b] = [hf[t][b], hb[L_b-1-t][b]] for t < L_b, 0 behind; y_rev[t][b] = y[L_b-1-t][b], the next layer's reversed
+    input, from the same pass (pk_seq_join_len, one launch).  hb = None: hf is [T, 2B, H], the directions its two halves
+    along dim 1.  Returns (y, y_rev), None for one not asked for; cat = True: ONE tensor [T, 2B, 2H] =
+    cat([y, y_rev], dim=1), the next shared-weight layer's rows."""
+    if hb is None:
+        if hf.dim() != 3 or hf.shape[1] % 2 != 0:
+            raise _lib.PkError("seq_join_len: one tensor holds both directions as [T, 2B, H] (got %s)" % (tuple(hf.shape),))
+        hf = hf.detach().contiguous()
+        B = hf.shape[1] // 2
+        hf, hb, ldi = hf[:, :B], hf[:, B:], 2 * B * hf.shape[2]
+    else:
+        if hb.shape != hf.shape:
+            raise _lib.PkError("seq_join_len: the directions differ in shape: %s and %s" % (tuple(hf.shape), tuple(hb.shape)))
+        hf, hb = hf.detach().contiguous(), hb.detach().contiguous()
+        ldi = hf.shape[1] * hf.shape[2]
+    _need_gpu(hb)
+    lens = _lens_arg("seq_join_len", lens, hf)
+    T, B, H = hf.shape
+    if cat:
+        full = _new(T, 2 * B, 2 * H, like=hf)
+        y, y_rev, ldo = full[:, :B], full[:, B:], 4 * B * H
+    else:
+        if not (want_y or want_rev):
+            raise _lib.PkError("seq_join_len: neither the joined tensor nor its reversal is asked for")
+        y = _new(T, B, 2 * H, like=hf) if want_y else None
+        y_rev = _new(T, B, 2 * H, like=hf) if want_rev else None
+        ldo = 2 * B * H
+    _lib.check(_lib.load().pk_seq_join_len(_stream(), _p(hf), _p(hb), ldi, _p(lens.device_tensor(hf.device)), T, B, H, _p(y),
+                                           _p(y_rev), ldo), "pk_seq_join_len")
+    return full if cat else (y, y_rev)
+
+
 class LnLastActDropFn(torch.autograd.Function):
     """drop(act(LayerNorm(z))) behind a conv layer's max-pool as ONE launch each way (pk_ln_last_act_drop_*), the CNN /
     SincNet flavour of the reference's LayerNorm (features [C, L], statistics over the last dim:

@@ -558,10 +558,12 @@ class _Recurrent(nn.Module):
         side_w, side_u = edge and F_.side_targets_any_ok(wps), edge and F_.side_targets_any_ok(ups)
         return _gate_matrix(wps, side_w, side_w), _gate_matrix(ups, side_u, side_u), side_w, side_u
 
-    def _layer(self, i, x, xb, xseg, mask_i, scalar_i, route, keep_y):
+    def _layer(self, i, x, xb, xseg, mask_i, scalar_i, route, keep_y, bidir=None):
         """Layer i on x: (y, bf16 copy of y or None, its segments).  xb / xseg: the bf16 copy the layer below published
-        (perf node), mask_i / scalar_i: the drop mask, keep_y: functional.rec_keep_y."""
+        (perf node), mask_i / scalar_i: the drop mask, keep_y: functional.rec_keep_y.  bidir: None = self.bidir; False runs a
+        bidirectional class's layer as a unidirectional one on rows that already hold both directions (_stack_lens)."""
         H = self._lay[i]
+        bidir = bool(self.bidir) if bidir is None else bool(bidir)
         wps, ups, bcat = self._layer_params(i)
         gamma = beta = rmean = rvar = None
         use_bn = bool(self._use_bn[i])
@@ -582,7 +584,7 @@ class _Recurrent(nn.Module):
             if not self.training:
                 rmean = torch.cat([b.running_mean for b in bns], 0)
                 rvar = torch.cat([b.running_var for b in bns], 0)
-        if use_bn and self.training and x.shape[0] * x.shape[1] * (2 if self.bidir else 1) <= 1:
+        if use_bn and self.training and x.shape[0] * x.shape[1] * (2 if bidir else 1) <= 1:
             # what torch's BatchNorm1d raises for the reference in the same situation (one row, training mode)
             raise ValueError("Expected more than 1 value per channel when training, got input size %s"
                              % (tuple(x.shape),))
@@ -592,7 +594,7 @@ class _Recurrent(nn.Module):
         # already being reduced).  Some other input must still carry the autograd edge that makes backward run at all:
         # the BatchNorm affine or the bias - one of the two always exists, neural_networks.py:1052-1055 - or x itself
         edge = torch.is_grad_enabled() and (use_bn or bcat is not None or x.requires_grad)
-        base = (self.KIND, self._act[i], H, bool(self.bidir), use_bn, self.training, 1e-5, 0.05, scalar_i)
+        base = (self.KIND, self._act[i], H, bidir, use_bn, self.training, 1e-5, 0.05, scalar_i)
         if route.perf:
             Wcat, Ucat, side_w, side_u = self._layer_matrices(wps, ups, True, edge)
             # training-mode BatchNorm: the running statistics of every gate's module are updated by the launch that
@@ -607,7 +609,7 @@ class _Recurrent(nn.Module):
             y, bmean, bvar, xb = F_.RecLayerPerfFn.apply(x, xb, Wcat.detach() if side_w else Wcat, bcat,
                                                        Ucat.detach() if side_u else Ucat, gamma, beta, rmean, rvar,
                                                        mask_i, cfg, edge_t)
-            xseg = (2 if self.bidir else 1, H, (H + 7) // 8 * 8)
+            xseg = (2 if bidir else 1, H, (H + 7) // 8 * 8)
             if stats_in_kernel:
                 return y, xb, xseg
         else:
@@ -619,7 +621,7 @@ class _Recurrent(nn.Module):
                                                            route=route))
             xb = xseg = None
         if use_bn and self.training:
-            n = x.shape[0] * x.shape[1] * (2 if self.bidir else 1)
+            n = x.shape[0] * x.shape[1] * (2 if bidir else 1)
             with torch.no_grad():  # BatchNorm1d(momentum=0.05) running statistics, per gate: four multi-tensor launches
                 means, vars_ = [b.running_mean for b in bns], [b.running_var for b in bns]
                 torch._foreach_mul_(means + vars_, 0.95)
@@ -631,6 +633,7 @@ class _Recurrent(nn.Module):
     def forward(self, x, drop_masks=None):
         if not x.is_cuda:
             raise PkError("pytorch-kaldi_amd.nn.%s runs on the GPU only: set use_cuda=True" % type(self).__name__)
+        lens = self._lengths_in_force(x)
         if self._use_ln_inp:
             x = self.ln0(x)
         if self._use_bn_inp:
@@ -645,6 +648,8 @@ class _Recurrent(nn.Module):
         xb = xseg = None  # perf mode: bf16 copy of the running activation, handed from layer to layer
         routes = [F_.rec_route(self.KIND, self._lay[i], bool(self._use_ln[i]), bool(self._use_bn[i]), self.training)
                   for i in range(self._n_lay)]
+        if lens is not None and self.bidir:
+            return self._stack_lens(x, lens, masks, scalars, routes)
         for i, route in enumerate(routes):
             mask_i, scalar_i = (masks[i], scalars[i]) if masks is not None else self._drop_mask(i, batch, x.device)
             x, xb, xseg = self._layer(i, x, xb, xseg, mask_i, scalar_i, route,
@@ -652,6 +657,37 @@ class _Recurrent(nn.Module):
         if xb is not None:  # the bf16 copy the last layer published: a perf-mode Linear behind it uses it as its operand
             x._pk_twin = (xb, xseg, x._version)
         return x
+
+    def _lengths_in_force(self, x):
+        """The functional.sentence_lengths block this call runs under, checked against x on the host, or None.  A batch of
+        padded sentences is a forward-only affair of an eval-mode module: batch statistics over padding rows are not the
+        sentence's."""
+        lens = F_.current_lengths()
+        if lens is None:
+            return None
+        name = type(self).__name__
+        if self.training:
+            raise PkError("%s: a batch with sentence lengths needs the module in eval mode (training-mode normalisation "
+                          "would take its statistics over the padding too)" % name)
+        lens.check(name, x)
+        return lens
+
+    def _stack_lens(self, x, lens, masks, scalars, routes):
+        """The bidirectional stack on a zero-padded batch of sentences of different lengths (functional.sentence_lengths),
+        literally the reference's cat([x, flip(x)], dim=1) (neural_networks.py:1083-1085) with the flip taken sentence by
+        sentence: every layer runs as a UNIDIRECTIONAL layer on 2B rows - the batch, and behind it every sentence reversed
+        on its own (functional.seq_pack_len) - with the weights both directions share anyway, and functional.seq_join_len
+        puts h[t][b] and h[L_b-1-t][B+b] side by side and writes the next layer's 2B rows in the same pass.  The
+        recurrences themselves are untouched.  The input projection runs over 2B rows here (the bidirectional kernels
+        project the B rows once); no bf16 copy crosses a join and no _pk_twin is set, as in _Cudnn."""
+        batch = x.shape[1]
+        x = F_.seq_pack_len(x, lens, cat=True)
+        for i, route in enumerate(routes):
+            mask_i, scalar_i = (masks[i], scalars[i]) if masks is not None else self._drop_mask(i, batch, x.device)
+            h = self._layer(i, x, None, None, mask_i, scalar_i, route, True, bidir=False)[0]
+            if i == self._n_lay - 1:
+                return F_.seq_join_len(h, None, lens)[0]
+            x = F_.seq_join_len(h, None, lens, cat=True)
 
 
 class liGRU(_Recurrent):
@@ -903,6 +939,11 @@ class _Cudnn(_Recurrent):
             raise PkError("pytorch-kaldi_amd.nn.%s runs on the GPU only: set use_cuda=True" % type(self).__name__)
         T, B, _ = x.shape
         L, ndir, H = self.num_layers, self._ndir, self.hidden_size
+        # a batch of sentences of different lengths (functional.sentence_lengths; eval mode, so no mask): the backward
+        # direction reads every sentence reversed on its own, and the joins turn it back the same way
+        lens = self._lengths_in_force(x)
+        if ndir == 1:
+            lens = None  # (causal: a sentence's rows do not depend on what follows them)
         masks, scale = None, 1.0
         if self.training and self.dropout > 0.0 and L > 1:
             scale = float(np.float32(1.0 / (1.0 - self.dropout)))  # rounded to fp32 once, here
@@ -912,11 +953,17 @@ class _Cudnn(_Recurrent):
                 masks = self._draw_masks(T, B, x.device)
         route = F_.rec_route(self.KIND, H, False, False, self.training)
         inp_f = x
-        inp_b = F_.seq_join(x, want_y=False, want_rev=True)[1] if ndir == 2 else None
+        if lens is not None:
+            inp_b = F_.seq_pack_len(x, lens, want_f=False)[1]
+        else:
+            inp_b = F_.seq_join(x, want_y=False, want_rev=True)[1] if ndir == 2 else None
         for k in range(L):
             last = k == L - 1
             yf = self._layer(k * ndir, inp_f, None, None, None, 1.0, route, True)[0]
             yb = self._layer(k * ndir + 1, inp_b, None, None, None, 1.0, route, True)[0] if ndir == 2 else None
+            if lens is not None:
+                inp_f, inp_b = F_.seq_join_len(yf, yb, lens, True, not last)
+                continue
             m = masks[k] if (masks is not None and not last) else None
             if ndir == 1 and m is None:
                 inp_f = yf
