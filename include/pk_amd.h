@@ -531,6 +531,23 @@ int pk_seq_pack_len(void* stream, const float* x, const int32_t* lens, int64_t T
 int pk_seq_join_len(void* stream, const float* hf, const float* hb, int64_t ldi, const int32_t* lens, int64_t T, int64_t B,
                     int64_t H, float* y_f, float* y_r, int64_t ldo);
 
+/* ---- posterior normalisation of a decoded batch (pk_seqlen.hip): the reference subtracts the log-priors from every
+ * sentence's log-posteriors on the host, out_save - np.log(counts / np.sum(counts)) (core.py:665-668), before it writes
+ * the matrix.  Here one pass over the head's output does that and drops the padding rows of a batch:
+ *     out[i][c] = (T)x[rows ? rows[i] : i][c] - logprior[c]          i < n, c < C
+ *   x         fp32 [R][C], dense: the head's output (R = max_len * B for a padded batch)
+ *   rows      int64 [n] in DEVICE memory, or NULL: the rows of x that hold frames, in the order they are written
+ *             (sentence after sentence); NULL = every row in place, n must equal R
+ *   logprior  [C], out [n][C], dense: both double (f64 != 0) or both float (f64 == 0) - the type numpy's expression has
+ *             for float64 or float32 counts (data_io.load_counts gives float32).  The log-priors are computed on the host.
+ * The widening is exact and the one IEEE subtraction is correctly rounded, so the result equals numpy's bit for bit.
+ * One launch; 4 bytes read and sizeof(T) written per element, 16-byte stores when out is 16-byte aligned (the output is
+ * indexed flat: a store may straddle two rows; rows of x need no alignment).  A row index outside 0 .. R-1 is clamped
+ * into that range by the kernel (the caller checks on the host): no index leaves x whatever rows holds.  Bad arguments -
+ * a required pointer NULL, a size below 1, no row map with n != R - return 2 and launch nothing. */
+int pk_post_normalize(void* stream, const float* x, const int64_t* rows, int64_t R, int64_t n, int64_t C,
+                      const void* logprior, void* out, int f64);
+
 /* persistent-recurrence health: number of spin time-outs since the last reset
  * (host-mapped counter, readable without a device sync). */
 unsigned pk_persist_error_count(void);

@@ -140,6 +140,7 @@ SIGNATURES = {
     "pk_seq_join_bwd": (c_int, [P, P, P, P, c_float, c_int64, c_int64, c_int64, c_int, P, P]),
     "pk_seq_pack_len": (c_int, [P, P, P, c_int64, c_int64, c_int64, P, P, c_int64]),
     "pk_seq_join_len": (c_int, [P, P, P, c_int64, P, c_int64, c_int64, c_int64, P, P, c_int64]),
+    "pk_post_normalize": (c_int, [P, P, P, c_int64, c_int64, c_int64, P, P, c_int]),
     "pk_persist_error_count": (ctypes.c_uint, []),
     "pk_persist_error_reset": (None, []),
     "pk_linear_bn_act_bf16_covers": (c_int, [c_int64, c_int64, c_int64]),

@@ -11,7 +11,10 @@ as ``core``.  What differs from the reference is ever
   (T, B, D) batch from the resident chunk;
 * fused flat-bucket optimizers whose state dicts stay torch.optim-compatible, so ``.pkl`` checkpoints written here
   load in the reference and vice versa;
-* rank 0 alone writes the ``.pkl`` / ``.info`` / ``.ark`` files.
+* rank 0 alone writes the ``.pkl`` / ``.info`` files;
+* a ``to_do = forward`` chunk is decoded by all ranks, each a contiguous run of its sentence groups
+  (``forward_shards``): rank 0 writes the ``.ark`` files, the others part files beside them, which rank 0 appends in rank
+  order (the output folder is shared between the ranks); log-priors are subtracted on the device (``pk_post_normalize``).
 
 The chunk reader stays the reference's (Kaldi pipes, data_io.read_lab_fea): it is looked up as ``data_io.read_lab_fea``
 on ``sys.path`` unless a ``reader`` callable with the same signature is passed in.
@@ -19,6 +22,7 @@ on ``sys.path`` unless a ``reader`` callable with the same signature is passed i
 import configparser
 import os
 import random
+import shutil
 import struct
 import sys
 import threading
@@ -93,6 +97,53 @@ def forward_groups(lengths, n):
     if n < 1:
         raise ValueError("forward_groups: n = %r sentences per group" % (n,))
     return [(s, min(s + n, len(lengths)), max(lengths[s:s + n])) for s in range(0, len(lengths), n)]
+
+
+def forward_shards(lens_all, n, world, seq_model):
+    """The groups of forward_groups(lens_all, n) dealt to `world` ranks: one list per rank, each a CONTIGUOUS run of the
+    groups, in order - the finished ark is the ranks' parts one after the other.  The runs are cut at the quantiles of the
+    cumulative cost: the first group in front of which at least r / world of the total cost lies starts rank r - but never
+    the group that started rank r - 1, so a rank is empty only when no groups are left (more ranks than groups: the
+    trailing ones).  A group costs its padded frames, max_len * nb, for a sequence model and its frames otherwise; no rank
+    gets more than total / world + the dearest group."""
+    if world < 1:
+        raise ValueError("forward_shards: world = %r ranks" % (world,))
+    lens = [int(v) for v in lens_all]
+    groups = forward_groups(lens, n)
+    cost = [t * (e - s) if seq_model else sum(lens[s:e]) for s, e, t in groups]
+    total, before, starts, g = sum(cost), 0, [0], 0
+    for r in range(1, world):
+        while g < len(groups) and (before * world < r * total or g <= starts[-1]):
+            before += cost[g]
+            g += 1
+        starts.append(g)
+    starts.append(len(groups))
+    return [groups[starts[r]:starts[r + 1]] for r in range(world)]
+
+
+def merge_parts(final_path, part_paths):
+    """Append the part files to the final file, in the order given, and remove them.  Ark records are self-delimiting, so
+    the bytes are those of one writer writing every record in that order."""
+    with open(final_path, "ab") as out:
+        for p in part_paths:
+            with open(p, "rb") as f:
+                shutil.copyfileobj(f, out, 1 << 22)
+    for p in part_paths:
+        os.remove(p)
+
+
+def all_ranks_ok(ok, world, device):
+    """The one collective of a forward chunk: MIN over the ranks' "my part is written and closed" flags.  It is the barrier
+    in front of the merge as well, and every rank reaches it whether its own loop raised or not."""
+    if world <= 1:
+        return bool(ok)
+    on_host = torch.distributed.get_backend() != "nccl"  # (gloo reduces host tensors; RCCL needs the flag on the device)
+    flag = torch.tensor([1 if ok else 0], dtype=torch.int32, device="cpu" if on_host else device)
+    torch.distributed.all_reduce(flag, op=torch.distributed.ReduceOp.MIN)
+    return int(flag.item()) == 1
+
+
+last_forward = None  # what this rank did in the last forward chunk: {"rank", "world", "groups", "sentences", "frames"}
 
 
 def padded_rows(lengths, max_len):
@@ -286,6 +337,7 @@ def run_nn_dp(data_name, data_set, data_end_index, fea_dict, lab_dict, arch_dict
               next_config_file, reader=None):
     """Process one chunk as ``[exp] to_do`` says (train / valid / forward) and return the next chunk's
     ``[data_name, data_set, data_end_index, fea_dict, lab_dict, arch_dict]`` (core.py:753)."""
+    global last_forward
     if not os.path.exists(cfg_file):
         sys.stderr.write("ERROR: The config file %s does not exist!\n" % (cfg_file))
         sys.exit(0)
@@ -344,11 +396,9 @@ def run_nn_dp(data_name, data_set, data_end_index, fea_dict, lab_dict, arch_dict
     seq_model = is_sequential_dict(config, arch_dict)
     reducer = make_reducer(nns, optimizers, world, launch_bound=not seq_model) if to_do == "train" else None
 
-    post_file = {}
-    if to_do == "forward" and rank == 0:
-        for out_id, name in enumerate(forward_outs):
-            suffix = "_to_decode.ark" if require_decodings[out_id] else ".ark"
-            post_file[name] = open(info_file.replace(".info", "_" + name + suffix), "wb")
+    # (a forward chunk fills these inside its try block, below: a rank that fails to open a file or to read the counts
+    # must still reach the ranks' one collective)
+    post_file, post_path, logprior, logprior_dev = {}, {}, {}, {}
 
     if seq_model or to_do == "forward":
         N_batches = int(len(data_name) / batch_size)
@@ -357,8 +407,6 @@ def run_nn_dp(data_name, data_set, data_end_index, fea_dict, lab_dict, arch_dict
     end = np.asarray(data_end_index, dtype=np.int64)
     assembler = BatchAssembler(data_set, data_end_index, device) if seq_model else None
     local, cols = rank_columns(batch_size, rank, world) if to_do != "forward" else (1, np.arange(1))
-    counts = {i: load_counts(forward_count_files[i]) for i in range(len(forward_outs))
-              if to_do == "forward" and forward_normalize_post[i]}
 
     def train_step(inp_):
         # (a training step - forward and the backward pass that accumulates into .grad: kernels may add to the flat
@@ -391,65 +439,111 @@ def run_nn_dp(data_name, data_set, data_end_index, fea_dict, lab_dict, arch_dict
     start_time = time.time()
     loss_sum = torch.zeros((), device=device)
     err_sum = torch.zeros((), device=device)
-    snt_index, beg_snt = 0, 0
+    snt_index = 0
     fence = F_.StepFence()  # eager steps: at most PK_STEPS_IN_FLIGHT of them enqueued ahead of the GPU
 
-    def forward_batched(n):
-        # PK_FORWARD_BATCH = n > 1: n consecutive sentences per forward_model call.  A sequence model takes them as ONE
-        # end-padded (max_len, nb, .) batch under functional.sentence_lengths (left offset 0, `random` is not consumed);
-        # anything else takes their frames back to back.  The frames of the group's outputs come back in ONE
-        # device-to-host copy and are written sentence by sentence, as the loop below writes them.
-        lens_all = sentence_lengths(end)
-        for s, e, max_len in forward_groups(lens_all, n):
+    def forward_chunk(groups, batched):
+        # This rank's groups of a `to_do = forward` chunk.  batched (PK_FORWARD_BATCH = n > 1): the sentences of a group in
+        # one forward_model call.  A sequence model takes them as ONE end-padded (max_len, nb, .) batch under
+        # functional.sentence_lengths (left offset 0, `random` is not consumed); anything else takes their frames back to
+        # back.  Otherwise a group is one sentence and goes through the way the reference's loop sends it.  An output that
+        # is normalised leaves the device as log-posterior minus log-prior with the padding rows gone (one launch);
+        # the others leave as they are, the padding dropped by a gather.  One device-to-host copy per output and group,
+        # written sentence by sentence.
+        done = {"groups": 0, "sentences": 0, "frames": 0}
+        for s, e, max_len in groups:
             lens, nb = [int(v) for v in lens_all[s:e]], e - s
-            frames = data_set[int(end[s]) - lens[0]:int(end[e - 1]), :].to(device)
-            if seq_model:
-                rows = torch.from_numpy(padded_rows(lens, max_len)).to(device)
-                inp = torch.zeros(max_len * nb, frames.shape[1], device=device).index_copy_(0, rows, frames)
-                with torch.no_grad(), F_.sentence_lengths(lens):
-                    outs_dict = forward_model(fea_dict, lab_dict, arch_dict, model, nns, costs, inp.view(max_len, nb, -1),
-                                              inp_out_dict, max_len, nb, to_do, forward_outs)
-                outs = [outs_dict[name].detach().reshape(max_len * nb, -1).index_select(0, rows) for name in forward_outs]
-            else:
-                with torch.no_grad():
-                    outs_dict = forward_model(fea_dict, lab_dict, arch_dict, model, nns, costs, frames.contiguous(),
-                                              inp_out_dict, 0, 1, to_do, forward_outs)
-                outs = [outs_dict[name].detach() for name in forward_outs]
-            widths = np.cumsum([0] + [o.shape[1] for o in outs])
-            host = (outs[0] if len(outs) == 1 else torch.cat(outs, 1)).cpu().numpy()
+            frames = data_set[int(end[s]) - lens[0]:int(end[e - 1]), :].contiguous().to(device)
+            rows = rows_host = None
+            with torch.no_grad():
+                if not batched:
+                    outs_dict = forward_model(fea_dict, lab_dict, arch_dict, model, nns, costs, frames.view(lens[0], 1, -1)
+                                              if seq_model else frames, inp_out_dict, lens[0] if seq_model else 0, 1, to_do,
+                                              forward_outs)
+                elif seq_model:
+                    rows_host = padded_rows(lens, max_len)
+                    rows = torch.from_numpy(rows_host).to(device)
+                    inp = torch.zeros(max_len * nb, frames.shape[1], device=device).index_copy_(0, rows, frames)
+                    with F_.sentence_lengths(lens):
+                        outs_dict = forward_model(fea_dict, lab_dict, arch_dict, model, nns, costs, inp.view(max_len, nb, -1),
+                                                  inp_out_dict, max_len, nb, to_do, forward_outs)
+                else:
+                    outs_dict = forward_model(fea_dict, lab_dict, arch_dict, model, nns, costs, frames, inp_out_dict, 0, 1,
+                                              to_do, forward_outs)
+            outs = []
+            for out_id, name in enumerate(forward_outs):
+                o = outs_dict[name].detach()
+                if rows is not None:
+                    o = o.reshape(max_len * nb, -1)
+                if out_id in logprior_dev:
+                    o = F_.post_normalize(o, logprior_dev[out_id], rows, rows_host)
+                elif rows is not None:
+                    o = o.index_select(0, rows)
+                outs.append(o)
+            host = [o.cpu().numpy() for o in outs]
             beg = 0
             for k in range(nb):
                 for out_id, name in enumerate(forward_outs):
-                    out_save = host[beg:beg + lens[k], widths[out_id]:widths[out_id + 1]]
-                    if forward_normalize_post[out_id]:
-                        c = counts[out_id]
-                        out_save = out_save - np.log(c / np.sum(c))
+                    out_save = host[out_id][beg:beg + lens[k]]
+                    if out_id in logprior and out_id not in logprior_dev:
+                        out_save = out_save - logprior[out_id]
                     write_mat(post_file[name], out_save, data_name[s + k])
                 beg += lens[k]
+            done["groups"] += 1
+            done["sentences"] += nb
+            done["frames"] += sum(lens)
+        return done
 
-    n_forward = forward_batch() if to_do == "forward" else 1
-    if n_forward > 1:
+    if to_do == "forward":
+        # Every rank decodes its own run of groups (forward_shards) and writes them with the same write_mat.  No collective
+        # inside the loop and no float ever crosses ranks: ONE all-reduce of an "ok" flag once the files are closed, reached
+        # whether this rank's loop raised or not, then rank 0 appends the parts in rank order - the bytes of a one-rank run.
+        n_forward = forward_batch()
+        lens_all = sentence_lengths(end)
+        ok = False
+        try:
+            # rank 0 writes the final ark, rank r > 0 its part beside it (merged below)
+            for out_id, name in enumerate(forward_outs):
+                suffix = "_to_decode.ark" if require_decodings[out_id] else ".ark"
+                post_path[name] = info_file.replace(".info", "_" + name + suffix)
+                post_file[name] = open(post_path[name] + ("" if rank == 0 else ".part%d" % rank), "wb")
+            # log-priors of the outputs that are normalised: once per chunk, on the host, the reference's expression
+            # (core.py:668) - and subtracted on the device, in the pass that strips the padding (PK_EXPERIMENT
+            # post_norm_device=0: on the host)
+            for out_id in range(len(forward_outs)):
+                if forward_normalize_post[out_id]:
+                    c = load_counts(forward_count_files[out_id])
+                    logprior[out_id] = np.log(c / np.sum(c))
+            if _lib.experiment("post_norm_device", "1") != "0":
+                logprior_dev.update({i: torch.from_numpy(lp).to(device) for i, lp in logprior.items()})
+            done = forward_chunk(forward_shards(lens_all, n_forward, world, seq_model)[rank], n_forward > 1)
+            torch.cuda.synchronize()
+            _lib.raise_if_persist_failed()
+            ok = True
+        finally:
+            for f in post_file.values():
+                f.close()
+            all_ok = all_ranks_ok(ok, world, device)
+        if not all_ok:
+            raise RuntimeError("run_nn_dp: the forward chunk %s failed on another rank" % (cfg_file,))
+        last_forward = dict(done, rank=rank, world=world)
         if rank == 0:
-            forward_batched(n_forward)
-        N_batches = 0  # (the sentence-by-sentence loop below has nothing left to do)
+            for name in forward_outs:
+                merge_parts(post_path[name], [post_path[name] + ".part%d" % r for r in range(1, world)])
+            if world > 1:
+                sys.stderr.write("run_nn_dp: forward chunk on %d ranks, rank 0 took %d groups / %d sentences / %d frames\n"
+                                 % (world, done["groups"], done["sentences"], done["frames"]))
+        # (ranks above 0 go on from here while rank 0 merges: the finished ark and `.info` are rank 0's to hand on)
+        N_batches = 0  # (the batch loop below is the train / valid loop)
     for i in range(N_batches):
         max_len = 0
-        if to_do == "forward":
-            if rank != 0:
-                continue
-            snt_len = int(end[snt_index]) - beg_snt
-            inp = data_set[beg_snt:beg_snt + snt_len, :].contiguous().to(device)
-            beg_snt = int(end[snt_index])
-            snt_index += 1
-            if seq_model:
-                max_len, inp = snt_len, inp.view(snt_len, 1, -1)
-        elif seq_model:
+        if seq_model:
             max_len, inp = assembler.batch(snt_index, batch_size, cols)
             snt_index += batch_size
         else:
             b0 = i * batch_size + rank * local
             inp = data_set[b0:b0 + local, :].contiguous().to(device, non_blocking=True)
-        nb = local if to_do != "forward" else 1
+        nb = local
         if to_do == "train":
             if graphed is not None:
                 outs_dict = graphed(inp)
@@ -465,16 +559,8 @@ def run_nn_dp(data_name, data_set, data_end_index, fea_dict, lab_dict, arch_dict
             with torch.no_grad():
                 outs_dict = forward_model(fea_dict, lab_dict, arch_dict, model, nns, costs, inp, inp_out_dict, max_len, nb,
                                           to_do, forward_outs)
-        if to_do == "forward":
-            for out_id, name in enumerate(forward_outs):
-                out_save = outs_dict[name].detach().cpu().numpy()
-                if forward_normalize_post[out_id]:
-                    c = counts[out_id]
-                    out_save = out_save - np.log(c / np.sum(c))
-                write_mat(post_file[name], out_save, data_name[i])
-        else:
-            loss_sum += outs_dict["loss_final"].detach()
-            err_sum += outs_dict["err_final"].detach()
+        loss_sum += outs_dict["loss_final"].detach()
+        err_sum += outs_dict["err_final"].detach()
     # the only full host sync of the chunk (the reference syncs once per batch for its progress bar, core.py:689; eager
     # steps wait for the step four back - functional.StepFence)
     if to_do != "forward":
@@ -493,8 +579,6 @@ def run_nn_dp(data_name, data_set, data_end_index, fea_dict, lab_dict, arch_dict
         for net in nns.keys():
             checkpoint = {"model_par": nns[net].state_dict(), "optimizer_par": optimizers[net].state_dict()}
             torch.save(checkpoint, info_file.replace(".info", "_" + arch_dict[net][0] + ".pkl"))
-    for f in post_file.values():
-        f.close()
     if rank == 0:
         with open(info_file, "w") as text_file:
             text_file.write("[results]\n")
@@ -502,7 +586,7 @@ def run_nn_dp(data_name, data_set, data_end_index, fea_dict, lab_dict, arch_dict
                 text_file.write("loss=%s\n" % loss_tot.cpu().numpy())
                 text_file.write("err=%s\n" % err_tot.cpu().numpy())
             text_file.write("elapsed_time_chunk=%f\n" % elapsed_time_chunk)
-    if world > 1:
+    if world > 1 and to_do != "forward":  # (a forward chunk's ranks have met already: all_ranks_ok)
         torch.distributed.barrier()
 
     p.join()

@@ -10,6 +10,9 @@
 // workgroups, every output element is written exactly once.  The vector form needs widths and pitches that are multiples
 // of 4 floats and 16-byte aligned pointers; anything else takes the scalar form.  A length outside 0 .. T is clamped into
 // that range by the kernels (the callers check on the host): no index leaves the tensors whatever `lens` holds.
+//
+// Behind the head, pk_post_normalize subtracts the log-priors from the log-posteriors and drops the padding rows in one
+// more streaming pass (described at its kernel below).
 #include "pk_common.h"
 
 namespace {
@@ -89,6 +92,64 @@ inline unsigned blocks_for(long n) {
     return (unsigned)(b < PK_SEQLEN_MAX_BLOCKS ? b : PK_SEQLEN_MAX_BLOCKS);
 }
 
+// Posterior normalisation of a decoded batch, padding stripped in the same pass:
+//   out[i][c] = (T)x[rows ? rows[i] : i][c] - logprior[c]        T = float or double, the type of logprior and out
+// The OUTPUT is indexed flat: one unit = 16 bytes of it (V = 4 floats or 2 doubles), which may straddle two rows - C is
+// 1938, 48 or 3480 in the recipes, so rows of x are not 16-byte aligned and are read element by element (neighbouring
+// lanes read neighbouring addresses).  The last unit may be short.  A row index outside 0 .. R-1 is clamped into that
+// range (the caller checks on the host): no index leaves x whatever `rows` holds.  One conversion (exact) and one IEEE
+// subtraction per element, nothing to contract.
+template <typename T, int V>
+__global__ void __launch_bounds__(PK_SEQLEN_THREADS) post_normalize_kernel(const float* __restrict__ x,
+                                                                           const int64_t* __restrict__ rows, long R, long C,
+                                                                           const T* __restrict__ logprior, long total,
+                                                                           T* __restrict__ out) {
+    const long units = (total + V - 1) / V, stride = (long)gridDim.x * blockDim.x;
+    const bool narrow = total < 0xfffffff0L;  // (a 32-bit division where the flat index allows it)
+    for (long u = (long)blockIdx.x * blockDim.x + threadIdx.x; u < units; u += stride) {
+        const long e0 = u * V;
+        long i = narrow ? (long)((unsigned)e0 / (unsigned)C) : e0 / C;
+        long c = e0 - i * C;
+        T v[V];
+#pragma unroll
+        for (int k = 0; k < V; ++k) {
+            if (e0 + k < total) {
+                long r = rows != nullptr ? (long)rows[i] : i;
+                r = r < 0 ? 0 : (r >= R ? R - 1 : r);
+                v[k] = (T)x[r * C + c] - logprior[c];
+            } else {
+                v[k] = (T)0;
+            }
+            if (++c == C) { c = 0; ++i; }
+        }
+        if (V > 1 && e0 + V <= total) {
+            typedef T vec_t __attribute__((ext_vector_type(V)));
+            vec_t w;
+#pragma unroll
+            for (int k = 0; k < V; ++k) w[k] = v[k];
+            *reinterpret_cast<vec_t*>(out + e0) = w;
+        } else {
+#pragma unroll
+            for (int k = 0; k < V; ++k)
+                if (e0 + k < total) out[e0 + k] = v[k];
+        }
+    }
+}
+
+template <typename T>
+void post_normalize_launch(void* stream, const float* x, const int64_t* rows, long R, long n, long C, const void* logprior,
+                           void* out) {
+    constexpr int W = 16 / (int)sizeof(T);
+    const long total = n * C;
+    const dim3 block(PK_SEQLEN_THREADS);
+    if ((reinterpret_cast<uintptr_t>(out) & 15u) == 0)
+        hipLaunchKernelGGL((post_normalize_kernel<T, W>), dim3(blocks_for((total + W - 1) / W)), block, 0, pk_stream(stream), x, rows, R, C,
+                           static_cast<const T*>(logprior), total, static_cast<T*>(out));
+    else
+        hipLaunchKernelGGL((post_normalize_kernel<T, 1>), dim3(blocks_for(total)), block, 0, pk_stream(stream), x, rows, R, C,
+                           static_cast<const T*>(logprior), total, static_cast<T*>(out));
+}
+
 }  // namespace
 
 extern "C" int pk_seq_pack_len(void* stream, const float* x, const int32_t* lens, int64_t T, int64_t B, int64_t D, float* out_f,
@@ -130,6 +191,23 @@ extern "C" int pk_seq_join_len(void* stream, const float* hf, const float* hb, i
         hipLaunchKernelGGL(seq_join_len_kernel<4>, grid, block, 0, pk_stream(stream), hf, hb, (long)ldi / 4, lens, (long)T, (long)B, (long)H / 4, y_f, y_r, (long)ldo / 4);
     else
         hipLaunchKernelGGL(seq_join_len_kernel<1>, grid, block, 0, pk_stream(stream), hf, hb, (long)ldi, lens, (long)T, (long)B, (long)H, y_f, y_r, (long)ldo);
+    PK_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int pk_post_normalize(void* stream, const float* x, const int64_t* rows, int64_t R, int64_t n, int64_t C,
+                                 const void* logprior, void* out, int f64) {
+    PK_REQUIRE(R >= 1 && n >= 1 && C >= 1, "pk_post_normalize: R = %lld, n = %lld, C = %lld must be positive", (long long)R,
+               (long long)n, (long long)C);
+    PK_REQUIRE(x != nullptr && logprior != nullptr && out != nullptr, "pk_post_normalize: the input, the log-priors or the output are NULL");
+    PK_REQUIRE(rows != nullptr || n == R, "pk_post_normalize: without a row map the output has the input's %lld rows, not %lld",
+               (long long)R, (long long)n);
+    PK_REQUIRE(R <= (1LL << 40) / C && n <= (1LL << 40) / C, "pk_post_normalize: [%lld] and [%lld] rows of %lld are out of range",
+               (long long)R, (long long)n, (long long)C);
+    PK_REQUIRE((reinterpret_cast<uintptr_t>(out) & (f64 ? 7u : 3u)) == 0 && (reinterpret_cast<uintptr_t>(logprior) & (f64 ? 7u : 3u)) == 0,
+               "pk_post_normalize: the log-priors or the output are not aligned to their element size");
+    if (f64) post_normalize_launch<double>(stream, x, rows, (long)R, (long)n, (long)C, logprior, out);
+    else post_normalize_launch<float>(stream, x, rows, (long)R, (long)n, (long)C, logprior, out);
     PK_LAUNCH_CHECK();
     return 0;
 }

@@ -1765,6 +1765,52 @@ def seq_join_len(hf, hb=None, lens=None, want_y=True, want_rev=False, cat=False)
     return full if cat else (y, y_rev)
 
 
+def post_normalize(x, logprior_dev, rows=None, rows_host=None):
+    """Log-posteriors minus log-priors, the padding rows of a decoding batch dropped in the same pass
+    (pk_post_normalize, one launch): out[i] = x[rows[i]] - logprior_dev, out[i] = x[i] without a row map.
+    x: the head's fp32 output [R, C]; logprior_dev [C] on the same device, float64 or float32 - the result has its type,
+    as numpy's `x - np.log(counts / np.sum(counts))` has (float64 counts give a float64 matrix, the float32 counts of
+    data_io.load_counts a float32 one), and equals numpy's bit for bit; rows: int64 [n] on the device, what
+    core.padded_rows gives.  Every entry must lie in 0 .. R-1: that is checked HERE, before the launch - on rows_host, the
+    same map as a host array, when the caller still has it (no device sync), on `rows` otherwise - the slow path: rows.min()
+    and rows.max() are two device syncs in front of the launch."""
+    _need_gpu(x)
+    if x.dim() != 2:
+        raise _lib.PkError("post_normalize: the head's output is [rows, classes] (got %s)" % (tuple(x.shape),))
+    R, C = int(x.shape[0]), int(x.shape[1])
+    if not logprior_dev.is_cuda or logprior_dev.device != x.device:
+        raise _lib.PkError("post_normalize: the log-priors are on %s, the posteriors on %s" % (logprior_dev.device, x.device))
+    if logprior_dev.dtype not in (torch.float64, torch.float32):
+        raise _lib.PkError("post_normalize: log-priors are float64 or float32 (got %s)" % logprior_dev.dtype)
+    if logprior_dev.dim() != 1 or int(logprior_dev.shape[0]) != C:
+        raise _lib.PkError("post_normalize: %s log-priors for %d classes" % (tuple(logprior_dev.shape), C))
+    if R < 1 or C < 1:
+        raise _lib.PkError("post_normalize: an empty matrix %s" % (tuple(x.shape),))
+    n = R
+    if rows is not None:
+        if not rows.is_cuda or rows.device != x.device or rows.dtype != torch.int64 or rows.dim() != 1 or rows.numel() < 1:
+            raise _lib.PkError("post_normalize: the row map is a non-empty int64 vector on the posteriors' device "
+                               "(got %s %s on %s)" % (rows.dtype, tuple(rows.shape), rows.device))
+        n = int(rows.numel())
+        if rows_host is not None:
+            import numpy as np
+
+            rows_host = np.asarray(rows_host)
+            if rows_host.shape != (n,):
+                raise _lib.PkError("post_normalize: the host copy of the row map has %s entries, the map %d" % (rows_host.shape, n))
+            lo, hi = int(rows_host.min()), int(rows_host.max())
+        else:
+            lo, hi = int(rows.min()), int(rows.max())
+        if lo < 0 or hi >= R:
+            raise _lib.PkError("post_normalize: row map entries must lie in 0 .. %d (got %d .. %d)" % (R - 1, lo, hi))
+        rows = rows.contiguous()
+    x, logprior_dev = x.detach().contiguous(), logprior_dev.contiguous()
+    out = torch.empty(n, C, device=x.device, dtype=logprior_dev.dtype)
+    _lib.check(_lib.load().pk_post_normalize(_stream(), _p(x), _p(rows), R, n, C, _p(logprior_dev), _p(out),
+                                             1 if logprior_dev.dtype == torch.float64 else 0), "pk_post_normalize")
+    return out
+
+
 class LnLastActDropFn(torch.autograd.Function):
     """drop(act(LayerNorm(z))) behind a conv layer's max-pool as ONE launch each way (pk_ln_last_act_drop_*), the CNN /
     SincNet flavour of the reference's LayerNorm (features [C, L], statistics over the last dim:

@@ -11,7 +11,17 @@ recurrent stack alone, no head and no copy (`trunk_ms`).  Windows alternate betw
 the whole set `--passes` times, host clock around device synchronises, reported per pass - `--rounds` windows each after a warm-up window; the figure
 reported is the median, with the spread, in bf16 and in exact-fp32 mode.  `padding_share` is the fraction of the padded
 batches' rows that hold no frame; `speedup` is n = 1 over n, same process, same weights; `rel_diff_to_n1` is the
-norm-relative distance of the first 64 sentences' log-posteriors from the n = 1 loop's."""
+norm-relative distance of the first 64 sentences' log-posteriors from the n = 1 loop's.
+
+    python tools/time_batched_decode.py --tail [--json profiles/forward_tail.json]
+
+times what follows the head in run_nn_dp instead, the part the figures above leave out: log-prior normalisation, padding
+strip, device-to-host copy and core.write_mat into /dev/null, for every sentence of the set.  The head's outputs of all
+groups (random log-posteriors of the right shapes) are resident before a window starts, so a window holds the tail only.
+Two arms per group size, in the same process, alternating: `host` - gather of the frame rows on the device, copy, numpy
+`out - logprior` per sentence (PK_EXPERIMENT post_norm_device=0) - and `device` - functional.post_normalize, copy
+(post_norm_device=1).  Both for the float32 log-priors data_io.load_counts leads to (the arks of the recipes are float32
+matrices) and for float64 ones (float64 counts: numpy widens every posterior and the ark holds doubles)."""
 import argparse
 import importlib
 import json
@@ -81,6 +91,87 @@ def decode(net, head, data, end, n, whole, keep=None):
     assert not whole or kept == int(end[-1])
 
 
+def tail_groups(lens, n, classes, seed):
+    """Per group: (lens, rows on the device or None, rows on the host, the head's output [R, classes] on the device)."""
+    gen = torch.Generator(device="cuda").manual_seed(seed)
+    out = []
+    for s, e, max_len in core.forward_groups(lens, n):
+        ls = [int(v) for v in lens[s:e]]
+        if n == 1:
+            rows = rows_host = None
+            R = ls[0]
+        else:
+            rows_host = core.padded_rows(ls, max_len)
+            rows = torch.from_numpy(rows_host).cuda()
+            R = max_len * len(ls)
+        out.append((ls, rows, rows_host, -30.0 * torch.rand(R, classes, device="cuda", generator=gen)))
+    return out
+
+
+def tail(groups, arm, lp_host, lp_dev, sink, keep=None):
+    """One pass over the set: what run_nn_dp does behind the head for a normalised output."""
+    for ls, rows, rows_host, x in groups:
+        if arm == "device":
+            host = F_.post_normalize(x, lp_dev, rows, rows_host).cpu().numpy()
+        else:
+            host = (x if rows is None else x.index_select(0, rows)).cpu().numpy()
+        beg = 0
+        for k, L in enumerate(ls):
+            m = host[beg:beg + L]
+            if arm == "host":
+                m = m - lp_host
+            core.write_mat(sink, m, "utt%05d" % k)
+            if keep is not None:
+                keep.append(m)
+            beg += L
+
+
+def tail_main(a):
+    ns = [int(v) for v in a.batches.split(",")]
+    lens = np.random.RandomState(0).randint(a.min_len, a.max_len + 1, size=a.sentences)
+    counts = np.random.RandomState(3).randint(1, 100000, size=a.classes)
+    out = {"mode": "tail", "sentences": a.sentences, "frames": int(lens.sum()), "lengths": [a.min_len, a.max_len],
+           "classes": a.classes, "rounds": a.rounds, "passes": a.passes, "device": torch.cuda.get_device_name(0),
+           "elements": int(lens.sum()) * a.classes, "sink": os.devnull}
+    with open(os.devnull, "wb") as sink:
+        for dtype in ("float32", "float64"):
+            c = counts.astype(dtype)
+            lp_host = np.log(c / np.sum(c))
+            lp_dev = torch.from_numpy(lp_host).cuda()
+            arms = [(n, arm) for n in ns for arm in ("host", "device")]
+            sets = {n: tail_groups(lens, n, a.classes, 10 + n) for n in ns}
+            for n in ns:  # same bytes first
+                got = {arm: [] for arm in ("host", "device")}
+                for arm in got:
+                    tail(sets[n][:4], arm, lp_host, lp_dev, sink, got[arm])
+                assert all(h.dtype == d.dtype == lp_host.dtype and np.array_equal(h, d) for h, d in zip(got["host"], got["device"]))
+            for n, arm in arms:  # warm-up window: allocator, pinned staging, first launch
+                tail(sets[n], arm, lp_host, lp_dev, sink)
+            torch.cuda.synchronize()
+            ms = {k: [] for k in arms}
+            for _ in range(a.rounds):
+                for n, arm in arms:
+                    torch.cuda.synchronize()  # (nothing of the previous arm's window is left on the device)
+                    t0 = time.perf_counter()
+                    for _ in range(a.passes):
+                        tail(sets[n], arm, lp_host, lp_dev, sink)
+                    torch.cuda.synchronize()
+                    ms[(n, arm)].append(1e3 * (time.perf_counter() - t0) / a.passes)
+            out[dtype] = {str(n): {arm: {"median": statistics.median(ms[(n, arm)]), "min": min(ms[(n, arm)]),
+                                         "max": max(ms[(n, arm)])} for arm in ("host", "device")} for n in ns}
+            for n in ns:
+                d = out[dtype][str(n)]
+                d["host_over_device"] = d["host"]["median"] / d["device"]["median"]
+            print(dtype, "tail_ms", json.dumps(out[dtype]), flush=True)
+            del sets
+    line = json.dumps(out)
+    print(line)
+    if a.json:
+        os.makedirs(os.path.dirname(os.path.abspath(a.json)), exist_ok=True)
+        with open(a.json, "w") as f:
+            f.write(line + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--sentences", type=int, default=192)
@@ -95,9 +186,12 @@ def main():
     ap.add_argument("--passes", type=int, default=2, help="passes over the set per timed window")
     ap.add_argument("--check", type=int, default=64, help="sentences whose outputs are compared between the batch sizes")
     ap.add_argument("--json", default=None)
+    ap.add_argument("--tail", action="store_true", help="time what follows the head: normalisation, copy, ark writer")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("time_batched_decode.py measures on the GPU; none is visible")
+    if a.tail:
+        return tail_main(a)
     ns = [int(v) for v in a.batches.split(",")]
     assert ns[0] == 1, "the baseline, n = 1, comes first"
     torch.manual_seed(1)
