@@ -13,6 +13,10 @@
  *  - all matrices are fp32 row-major.  `prec` selects the MFMA operand type of
  *    the GEMM-shaped work: PK_PREC_F32 = exact fp32 (v_mfma_f32_32x32x2_f32 /
  *    16x16x4_f32), PK_PREC_BF16 = bf16 operands with fp32 accumulation.
+ *    pk_gemm alone also takes PK_PREC_BF16X3: every fp32 operand split into
+ *    two bf16 (hi + lo) while staging, three bf16 MFMAs per product (lo.hi,
+ *    hi.lo, hi.hi) into one fp32 accumulator - about 16 mantissa bits per
+ *    operand.  Every other entry with a `prec` takes 0 / 1 only.
  *
  * Each group cites the reference code it replaces (paths relative to the
  * mravanelli/pytorch-kaldi checkout).
@@ -28,6 +32,7 @@ extern "C" {
 
 #define PK_PREC_F32 0
 #define PK_PREC_BF16 1
+#define PK_PREC_BF16X3 2 /* pk_gemm only */
 
 /* activations: neural_networks.py:36-57 (act_fun) */
 #define PK_ACT_LINEAR 0

@@ -6,17 +6,19 @@
 //
 //   C[M,N] = alpha * A(M,K) . B(K,N) + beta*C + bias
 //
-// Two operand precisions share the same staging skeleton:
+// Three operand precisions share the same staging skeleton:
 //   PREC_F32  v_mfma_f32_32x32x2_f32   exact fp32 (bitwise an fmaf chain)  - parity mode
 //   PREC_BF16 v_mfma_f32_32x32x16_bf16 operands rounded to bf16 while staging
 //             fp32 tiles into LDS, fp32 accumulate                          - perf mode
+//   PREC_BF16X3 the same instruction on operands split hi + lo while staging:
+//             four MFMAs per product, ~16 mantissa bits per operand         - bf16x3 mode (gemm_bf16x3_kernel)
 //
 // The exact-fp32 kernel has two forms with bit-identical results (every output element one fmaf chain over ascending
 // k): the register-staged first form below (any strides / alignment) and the LDS-DMA form (gemm_f32_dma_kernel: aligned
 // operands, 96-110 TFLOP/s of the pipe's 155 on the parity mode's shapes) - pk_gemm picks per call.
 // Block tile 128x128, 4 waves (2x2), wave tile 64x64 = 2x2 MFMA 32x32 tiles.
 // LDS layouts:  f32 : [BK=16][128+4] floats  (fragment reads = consecutive lanes, conflict free)
-//               bf16: [128][BK=32+8] bf16    (fragment reads = ds_read_b128, odd 16-B row stride)
+//               bf16: [128][BK=32+8] bf16    (fragment reads = ds_read_b128, odd 16-B row stride; bf16x3: a hi and a lo plane)
 // Operands may be contiguous along k (KC) or along m/n; the loader vectorises
 // along the contiguous direction and falls back to guarded scalar loads at
 // ragged edges / unaligned leading dimensions.
@@ -523,6 +525,191 @@ __global__ __launch_bounds__(256) void gemm_bf16_kernel(GemmArgs p) {
     store_acc(p, acc, m0, n0, wm, wn, lane, split);
 }
 
+// ---------------------------------------------------------------------------
+// bf16x3 kernel: near-fp32 products on the bf16 matrix pipe (fp32 in HBM, every value split in two bf16 while staging)
+//   v = hi + lo + e,  hi = bf16(v),  lo = bf16(v - hi)  (both round-to-nearest-even; v - hi is exact in fp32)
+//   a.b ~ a_lo.b_lo + a_lo.b_hi + a_hi.b_lo + a_hi.b_hi  - into ONE fp32 accumulator, small terms first
+// Kept from the plan: 128x128 block tile, 2x2 waves of 64x64 (2x2 MFMA 32x32x16 tiles), BK = 32, two LDS planes (hi, lo)
+// per operand of [128][BK + 8] bf16 (the odd 16-byte row stride of the bf16 kernel: conflict-free ds_read_b128 fragments),
+// double buffered: 2 operands x 2 planes x 2 buffers x 10 240 B = 80 KB, dynamic LDS - ONE or two workgroups per CU
+// (BK = 16 at 48 KB and three per CU measured 20 % slower); next tile's global loads in front of the MFMA block, split and
+// stored behind it; work_item, store_acc and splitk_reduce_kernel shared; K = 0 gives beta C + bias.
+// Changed: (1) the lo.lo product is KEPT - a fourth MFMA.  With round-to-nearest splits |lo| reaches 2^-8 |v| and |e| 2^-17 |v|
+// (a value just above a power of two), so the dropped a_lo.b_lo alone can cost 2^-16 |a.b|: on K = 32 products of operands
+// spread over twelve binades the three-term form missed the 2^-16 element bound by 2.5 %; with it the
+// per-product error is |e_a b| + |a e_b| <= 2^-16 |a.b|.  (2) an m/n-contiguous operand is fetched one dword per lane, row
+// per lane (SplitLoader<BK, false>), which turns its plane stores into conflict-free 16-byte writes.
+// ---------------------------------------------------------------------------
+// (x, y) -> packed hi pair and packed lo pair.  hi not finite (Inf, NaN, or a finite value that rounds beyond bf16's range):
+// lo = 0, so that the non-finite value reaches C through the hi plane alone and finite products next to it stay finite
+__device__ __forceinline__ void split_bf2(float x, float y, unsigned& hi, unsigned& lo) {
+    hi = pk_pack_bf2(x, y);
+    const float hx = __uint_as_float(hi << 16), hy = __uint_as_float(hi & 0xffff0000u);
+    const float rx = __builtin_fabsf(hx) < __builtin_inff() ? x - hx : 0.f;
+    const float ry = __builtin_fabsf(hy) < __builtin_inff() ? y - hy : 0.f;
+    lo = pk_pack_bf2(rx, ry);
+}
+
+// global -> register -> two LDS planes [128][LD] bf16 (hi, lo) of one operand tile
+template <int BK, bool KC>
+struct SplitLoader;
+
+// k-contiguous operand: TileLoader's float4 along k (guarded scalars at ragged edges / unaligned rows), 8-byte plane stores
+template <int BK>
+struct SplitLoader<BK, true> : TileLoader<BK, true> {
+    template <int LD>
+    __device__ __forceinline__ void store_bf16x2(unsigned short* __restrict__ hi, unsigned short* __restrict__ lo,
+                                                 int tid) const {
+#pragma unroll
+        for (int i = 0; i < this->NV; ++i) {
+            int r, k;
+            this->coord(tid + 256 * i, r, k);
+            uint2 h, l;
+            split_bf2(this->v[i].x, this->v[i].y, h.x, l.x);
+            split_bf2(this->v[i].z, this->v[i].w, h.y, l.y);
+            *reinterpret_cast<uint2*>(&hi[r * LD + k]) = h;  // 8-B aligned: LD*2 and k*2 multiples of 8
+            *reinterpret_cast<uint2*>(&lo[r * LD + k]) = l;
+        }
+    }
+};
+
+// m/n-contiguous operand: thread t owns row t & 127 and the k-half t >> 7 of the tile.  Every load is one dword per
+// lane - 64 consecutive rows, a 256-byte line per wave, any leading dimension or alignment, one guard per element - and
+// the thread ends up with BK/2 consecutive k of ONE row: 16-byte plane stores at the fragment reads' conflict-free row
+// stride (TileLoader's float4 along the rows would leave 2-byte stores that collide eight ways at this pitch)
+template <int BK>
+struct SplitLoader<BK, false> {
+    static constexpr int KH = BK / 2;
+    float v[KH];
+
+    __device__ __forceinline__ void load(const float* __restrict__ base, long rs, long cs, int r0, int k0, int rmax,
+                                         int kmax, int /*vec_ok*/, int tid) {
+        const int gr = r0 + (tid & 127), gk = k0 + (tid >> 7) * KH;
+        const float* p = base + (long)gr * rs + (long)gk * cs;
+        if (gr < rmax && gk + KH <= kmax) {  // (one branch per tile; the guarded form only at the ragged end of the reduction)
+#pragma unroll
+            for (int e = 0; e < KH; ++e) v[e] = p[e * cs];
+        } else {
+#pragma unroll
+            for (int e = 0; e < KH; ++e) v[e] = (gr < rmax && gk + e < kmax) ? p[e * cs] : 0.f;
+        }
+    }
+
+    template <int LD>
+    __device__ __forceinline__ void store_bf16x2(unsigned short* __restrict__ hi, unsigned short* __restrict__ lo,
+                                                 int tid) const {
+        const int at = (tid & 127) * LD + (tid >> 7) * KH;  // 16-B aligned: LD*2 and KH*2 multiples of 16
+#pragma unroll
+        for (int q = 0; q < KH / 8; ++q) {
+            uint4 h, l;
+            split_bf2(v[8 * q + 0], v[8 * q + 1], h.x, l.x);
+            split_bf2(v[8 * q + 2], v[8 * q + 3], h.y, l.y);
+            split_bf2(v[8 * q + 4], v[8 * q + 5], h.z, l.z);
+            split_bf2(v[8 * q + 6], v[8 * q + 7], h.w, l.w);
+            *reinterpret_cast<uint4*>(&hi[at + 8 * q]) = h;
+            *reinterpret_cast<uint4*>(&lo[at + 8 * q]) = l;
+        }
+    }
+};
+
+// The split's v - hi must stay a scalar subtraction: the kernel is compiled without the packed-fp32 VALU forms (this kernel
+// only - the attribute leaves the code of the kernels above as it was).  A function with another feature set takes in
+// nothing but always-inline callees, hence the barrier spelled out (what __syncthreads() expands to).
+#ifdef __HIP_DEVICE_COMPILE__
+#define PK_X3_TARGET __attribute__((target("no-packed-fp32-ops")))
+#else
+#define PK_X3_TARGET
+#endif
+__device__ __forceinline__ void x3_barrier() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    __builtin_amdgcn_s_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+}
+
+constexpr int X3_BK = 32, X3_LDS = 2 * 4 * BM * (X3_BK + 8) * (int)sizeof(unsigned short);  // 81 920 B
+
+template <bool A_KC, bool B_KC>
+__global__ __launch_bounds__(256) PK_X3_TARGET void gemm_bf16x3_kernel(GemmArgs p) {
+    constexpr int BK = X3_BK, LD = BK + 8, PL = BM * LD;  // one plane: [128][LD] bf16, rows an odd multiple of 16 B
+    extern __shared__ __attribute__((aligned(16))) unsigned short x3_planes[];  // [2 buffers][A hi, A lo, B hi, B lo][PL]
+
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int wm = wave >> 1, wn = wave & 1;
+    int m0, n0, split;
+    if (!work_item(p, m0, n0, split)) return;
+    const int kbeg = split * p.k_per_split;
+    const int kend = min(p.K, kbeg + p.k_per_split);
+    const int nk = (kend - kbeg + BK - 1) / BK;
+
+    f32x16 acc[2][2];
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+
+    SplitLoader<BK, A_KC> la;
+    SplitLoader<BK, B_KC> lb;
+    if (nk > 0) {
+        la.load(p.A, p.a_rs, p.a_cs, m0, kbeg, p.M, kend, p.vecA, tid);
+        lb.load(p.B, p.b_cs, p.b_rs, n0, kbeg, p.N, kend, p.vecB, tid);
+        la.template store_bf16x2<LD>(x3_planes, x3_planes + PL, tid);
+        lb.template store_bf16x2<LD>(x3_planes + 2 * PL, x3_planes + 3 * PL, tid);
+    }
+    x3_barrier();
+    const int arow = (wm * 64 + (lane & 31)) * LD + (lane >> 5) * 8;
+    const int brow = (wn * 64 + (lane & 31)) * LD + (lane >> 5) * 8;
+    for (int kt = 0; kt < nk; ++kt) {
+        const unsigned short* cur = x3_planes + (kt & 1) * 4 * PL;
+        unsigned short* nxt = x3_planes + ((kt + 1) & 1) * 4 * PL;
+        if (kt + 1 < nk) {
+            la.load(p.A, p.a_rs, p.a_cs, m0, kbeg + (kt + 1) * BK, p.M, kend, p.vecA, tid);
+            lb.load(p.B, p.b_cs, p.b_rs, n0, kbeg + (kt + 1) * BK, p.N, kend, p.vecB, tid);
+        }
+#pragma unroll
+        for (int ks = 0; ks < BK / 16; ++ks) {
+            // 32x32x16: lane supplies row lane & 31, k = (lane >> 5) * 8 .. + 8 - eight 16-byte reads for sixteen MFMAs
+            bf16x8 ah[2], al[2], bh[2], bl[2];
+#pragma unroll
+            for (int i = 0; i < 2; ++i) {
+                ah[i] = *reinterpret_cast<const bf16x8*>(&cur[arow + i * 32 * LD + ks * 16]);
+                al[i] = *reinterpret_cast<const bf16x8*>(&cur[PL + arow + i * 32 * LD + ks * 16]);
+                bh[i] = *reinterpret_cast<const bf16x8*>(&cur[2 * PL + brow + i * 32 * LD + ks * 16]);
+                bl[i] = *reinterpret_cast<const bf16x8*>(&cur[3 * PL + brow + i * 32 * LD + ks * 16]);
+            }
+            // per accumulator: lo.lo, lo.hi, hi.lo, then hi.hi (small terms first); term by term over the four accumulators,
+            // so that consecutive MFMAs never wait for each other's result
+#pragma unroll
+            for (int i = 0; i < 2; ++i)
+#pragma unroll
+                for (int j = 0; j < 2; ++j)
+                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[i], bl[j], acc[i][j], 0, 0, 0);
+#pragma unroll
+            for (int i = 0; i < 2; ++i)
+#pragma unroll
+                for (int j = 0; j < 2; ++j)
+                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[i], bh[j], acc[i][j], 0, 0, 0);
+#pragma unroll
+            for (int i = 0; i < 2; ++i)
+#pragma unroll
+                for (int j = 0; j < 2; ++j)
+                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[i], bl[j], acc[i][j], 0, 0, 0);
+#pragma unroll
+            for (int i = 0; i < 2; ++i)
+#pragma unroll
+                for (int j = 0; j < 2; ++j)
+                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[i], bh[j], acc[i][j], 0, 0, 0);
+        }
+        if (kt + 1 < nk) {
+            la.template store_bf16x2<LD>(nxt, nxt + PL, tid);
+            lb.template store_bf16x2<LD>(nxt + 2 * PL, nxt + 3 * PL, tid);
+        }
+        x3_barrier();
+    }
+    store_acc(p, acc, m0, n0, wm, wn, lane, split);
+}
+
 // split-K reduction: C = alpha * sum_s ws[s] + beta*C + bias
 __global__ void splitk_reduce_kernel(const float* __restrict__ ws, int splitk, int M, int N, float alpha, float beta,
                                      const float* __restrict__ bias, float* __restrict__ C, long ldc) {
@@ -555,7 +742,7 @@ extern "C" int pk_gemm(void* stream, int prec, int M, int N, int K, float alpha,
                (long)a_cs);
     PK_REQUIRE(b_rs == 1 || b_cs == 1, "pk_gemm: B must be contiguous along k or n (strides %ld,%ld)", (long)b_rs,
                (long)b_cs);
-    PK_REQUIRE(prec == PK_PREC_F32 || prec == PK_PREC_BF16, "pk_gemm: bad prec %d", prec);
+    PK_REQUIRE(prec == PK_PREC_F32 || prec == PK_PREC_BF16 || prec == PK_PREC_BF16X3, "pk_gemm: bad prec %d", prec);
     hipStream_t st = pk_stream(stream);
     GemmArgs p;
     p.M = M; p.N = N; p.K = K;
@@ -634,8 +821,17 @@ extern "C" int pk_gemm(void* stream, int prec, int M, int N, int K, float alpha,
     }
     if (dma) {
     } else if (prec == PK_PREC_F32) PK_LAUNCH_GEMM(gemm_f32_kernel);
-    else PK_LAUNCH_GEMM(gemm_bf16_kernel);
+    else if (prec == PK_PREC_BF16) PK_LAUNCH_GEMM(gemm_bf16_kernel);
 #undef PK_LAUNCH_GEMM
+    else {
+        // 80 KB of dynamic LDS: above the 64 KB default, granted once per instance
+        const void* k = a_kc ? (b_kc ? (const void*)gemm_bf16x3_kernel<true, true> : (const void*)gemm_bf16x3_kernel<true, false>)
+                             : (b_kc ? (const void*)gemm_bf16x3_kernel<false, true> : (const void*)gemm_bf16x3_kernel<false, false>);
+        const int rc = pk_grant_dynamic_lds(k, X3_LDS);
+        if (rc) return rc;
+        void* kargs[] = {&p};
+        PK_CHECK_HIP(hipLaunchKernel(k, grid, block, kargs, X3_LDS, st));
+    }
     PK_LAUNCH_CHECK();
     if (splitk > 1) {
         const long total = (long)M * N;

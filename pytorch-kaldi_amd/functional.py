@@ -14,7 +14,7 @@ import torch
 
 from . import _lib
 
-PREC = {"fp32": 0, "bf16": 1}
+PREC = {"fp32": 0, "bf16": 1, "bf16x3": 2}
 ACT = {"linear": 0, "relu": 1, "tanh": 2, "sigmoid": 3, "leaky_relu": 4, "elu": 5}
 CELL = {"liGRU": 0, "RNN": 1, "LSTM": 2, "GRU": 3, "minimalGRU": 4}
 REC_STEPWISE, REC_PERSISTENT = 0, 1
@@ -23,8 +23,10 @@ REC_STEPWISE, REC_PERSISTENT = 0, 1
 class _Settings:
     """Process-wide numerics / algorithm switches.
 
-    precision : "fp32" (exact fp32 MFMA - parity mode, default) or "bf16"
-                (bf16 MFMA operands, fp32 accumulate / state / master weights).
+    precision : "fp32" (exact fp32 MFMA - parity mode, default), "bf16"
+                (bf16 MFMA operands, fp32 accumulate / state / master weights) or "bf16x3" (the parity mode with
+                its pk_gemm products on the bf16 matrix pipe: operands split hi + lo, three MFMAs per product -
+                pk_gemm.hip; routes, recurrences and every other kernel are the fp32 mode's).
     rec_algo  : "auto" | "stepwise" | "persistent".
     """
 
@@ -381,14 +383,23 @@ def _small_m_splitk(M, N, K):
     return int(max(1, min(16, 512 // max(1, _tiles(M, N)), K // 64)))
 
 
+def entry_prec():
+    """The `prec` of every entry point other than pk_gemm (pk_rec_fwd / pk_rec_bwd and whatever else takes one): they know
+    PK_PREC_F32 and PK_PREC_BF16 only, and the bf16x3 mode runs them as the fp32 mode does."""
+    return PREC["fp32" if settings.precision == "bf16x3" else settings.precision]
+
+
 def gemm(M, N, K, A, a_rs, a_cs, B, b_rs, b_cs, C, ldc, alpha=1.0, beta=0.0, bias=None, splitk=1, prec=None):
     lib = _lib.load()
     ws = None
-    if splitk == 1 and a_cs == 1 and (prec or settings.precision) == "fp32":
+    prec = prec or settings.precision
+    if settings.precision == "bf16x3" and prec == "fp32":
+        prec = "bf16x3"  # the products that name fp32 (weight gradients outside the bf16 mode) are the mode's target too
+    if splitk == 1 and a_cs == 1 and prec in ("fp32", "bf16x3"):
         splitk = _small_m_splitk(M, N, K)
     if splitk > 1:
         ws = torch.empty(splitk * M * N, device=C.device, dtype=torch.float32)
-    rc = lib.pk_gemm(_stream(), PREC[prec or settings.precision], M, N, K, alpha, _p(A), a_rs, a_cs, _p(B), b_rs, b_cs,
+    rc = lib.pk_gemm(_stream(), PREC[prec], M, N, K, alpha, _p(A), a_rs, a_cs, _p(B), b_rs, b_cs,
                      beta, _p(C), ldc, _p(bias), splitk, _p(ws))
     _lib.check(rc, "pk_gemm")
     return C
@@ -2219,7 +2230,7 @@ class RecLayerFn(torch.autograd.Function):
         Y = _new(T, B, geom.ndir * H, like=x2)
         S = _new(geom.ndir, TB, geom.NS * H, like=x2)
         use_ln = ln_gamma is not None
-        prec = PREC[settings.precision]
+        prec = entry_prec()
         if route.algo == REC_PERSISTENT:
             _lib.raise_if_persist_failed()
         LNS, n_lnwork = None, 0
