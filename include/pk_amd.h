@@ -347,6 +347,23 @@ int pk_rec_fwd_bf16(void* stream, int cell, int act, int T, int B, int bidir, in
 int pk_rec_bwd_bf16(void* stream, int cell, int act, int T, int B, int bidir, int H, const float* U, const float* mask,
                     float mask_scalar, const float* Y, const float* S, const float* dY, float* dP2, uint16_t* dGb,
                     int64_t g_pitch, int prefilled);
+/* ... for a torch-layout bidirectional layer (LSTM_cudnn / RNN_cudnn, neural_networks.py:153-203, :256-297: one weight set
+ * per direction), BOTH directions in one launch (pk_rec_persist2_dirs.hip).  Geometry and arguments of the two entries
+ * above with bidir = 1 (R = 2B rows), except: P is [2][T*B][G*H] - slab d holds x . W_d^T indexed by ORIGINAL time, rows
+ * of direction 1 read slab 1 at row (T-1-t)*B + b; pscale / pshift are [2][G*H]; U is [2][G*H][H]; mask is NULL (no
+ * recurrent mask: mask_scalar alone).  Y, S, Yb, dP2, dGb, the pitches and `prefilled` are unchanged, S / Y may be NULL
+ * as above.  Clusters are direction-pure and both directions' clusters must be resident at once.  Cells PK_CELL_LSTM and
+ * PK_CELL_RNN, H <= 576, the kernel variants pk_rec_{fwd,bwd}_bf16 launch by default; every row's result is
+ * bit-identical to the single-direction launch of its direction.
+ * Return value 1: "not covered" - nothing was launched and no error is set, the caller runs one launch per direction
+ * (pk_rec_dirs_covered answers the same question up front: 1 = covered). */
+int pk_rec_dirs_covered(int cell, int act, int T, int B, int H);
+int pk_rec_fwd_bf16_dirs(void* stream, int cell, int act, int T, int B, int bidir, int H, const float* P,
+                         const float* pscale, const float* pshift, const float* U, const float* mask, float mask_scalar,
+                         float* Y, float* S, uint16_t* Yb, int64_t y_pitch, int prefilled);
+int pk_rec_bwd_bf16_dirs(void* stream, int cell, int act, int T, int B, int bidir, int H, const float* U, const float* mask,
+                         float mask_scalar, const float* Y, const float* S, const float* dY, float* dP2, uint16_t* dGb,
+                         int64_t g_pitch, int prefilled);
 /* ... with per-step LayerNorm of h_t inside the persistent time loop (liGRU / RNN / LSTM; the reference's
  * `if self.*_use_laynorm[i]: ht = self.ln[i](ht)`, neural_networks.py:466-467, :1138-1139, :1444-1445): every step
  * exchanges the rows' partial sums between the workgroups of a cluster a second time (fp32, 32 bytes per wave and row

@@ -18,6 +18,9 @@ OBJDIR = os.path.join(LIBDIR, "obj")
 LIB = os.path.join(LIBDIR, "libpk_amd.so")
 ARCH = "gfx950"
 FLAGS = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC"]
+# per-source additions: the packed-fp32 VALU forms (v_pk_add / mul / fma_f32) are kept out of the newer kernels
+NO_PK_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
+EXTRA_FLAGS = {"pk_rec_persist2_dirs.hip": NO_PK_F32}
 
 
 def _hipcc():
@@ -34,7 +37,7 @@ def _newest_header():
 
 
 def _compile(hipcc, src, obj):
-    cmd = [hipcc] + FLAGS + ["-c", src, "-o", obj]
+    cmd = [hipcc] + FLAGS + EXTRA_FLAGS.get(os.path.basename(src), []) + ["-c", src, "-o", obj]
     r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
     if r.returncode != 0:
         raise RuntimeError("hipcc failed on %s:\n%s" % (src, r.stdout))

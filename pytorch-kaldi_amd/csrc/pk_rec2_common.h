@@ -1,5 +1,6 @@
 // pk_rec2_common.h - shared device helpers of the perf-mode persistent recurrences
-// (pk_rec_persist2.hip: liGRU / RNN / LSTM; pk_rec_persist2_gru.hip: GRU / minimalGRU).
+// (pk_rec_persist2.hip: liGRU / RNN / LSTM; pk_rec_persist2_gru.hip: GRU / minimalGRU; pk_rec_persist2_dirs.hip: both
+// directions of a torch-layout LSTM / RNN layer in one launch).
 // See pk_rec_persist2.hip for the design notes.
 #pragma once
 #ifndef PK_REC2_PRECISE       // (pk_rec_persist2_f32.hip: the exact-fp32 twin keeps the precise exp / division)
@@ -167,6 +168,44 @@ __device__ __forceinline__ bool poll_to_lds(__amdgpu_buffer_rsrc_t rs, const uns
     }
 #pragma unroll
     for (int i = 0; i < NCH; ++i) *reinterpret_cast<u32x4*>(tile + loff[i]) = v[i];
+    return dead;
+}
+
+// poll_to_lds with the LDS destinations read from a per-thread LDS table (stride 512 entries per
+// slot) once the chunks have landed, instead of being held in registers across the whole step (the eight-wave kernels of
+// pk_rec_persist2_lstm.hip and pk_rec_persist2_dirs.hip)
+template <int NCH, bool FAST>
+__device__ __forceinline__ bool poll_to_lds_tab(__amdgpu_buffer_rsrc_t rs, const unsigned (&goff)[NCH], const int* ltab,
+                                                unsigned char* tile, unsigned* err, int spin_limit, int lane, bool dead,
+                                                int& retries) {
+    u32x4 v[NCH];
+#pragma unroll
+    for (int i = 0; i < NCH; ++i) v[i] = poll_load<FAST>(rs, goff[i]);
+    bool bad = false;
+#pragma unroll
+    for (int i = 0; i < NCH; ++i) bad = bad | has_sent16(v[i]);
+    if (__any(bad) && !dead) {
+        int spins = 0;
+        while (true) {
+#pragma unroll
+            for (int i = 0; i < NCH; ++i)
+                if (has_sent16(v[i])) v[i] = poll_load<FAST>(rs, goff[i]);
+            bad = false;
+#pragma unroll
+            for (int i = 0; i < NCH; ++i) bad = bad | has_sent16(v[i]);
+            ++retries;
+            if (!__any(bad)) break;
+            if (spin_check2(spins, spin_limit, err, lane)) {
+                dead = true;
+                break;
+            }
+        }
+    }
+    int lo[NCH];
+#pragma unroll
+    for (int i = 0; i < NCH; ++i) lo[i] = ltab[i * 512];
+#pragma unroll
+    for (int i = 0; i < NCH; ++i) *reinterpret_cast<u32x4*>(tile + lo[i]) = v[i];
     return dead;
 }
 

@@ -29,43 +29,6 @@ constexpr int LNS = 5;   // saved slots f, i, o, g, c
 constexpr int GW = 2;    // gates per wave
 constexpr int NWV = 8;   // waves per workgroup
 
-// poll_to_lds (pk_rec2_common.h) with the LDS destinations read from a per-thread LDS table (stride 512 entries per
-// slot) once the chunks have landed, instead of being held in registers across the whole step
-template <int NCH, bool FAST>
-__device__ __forceinline__ bool poll_to_lds_tab(__amdgpu_buffer_rsrc_t rs, const unsigned (&goff)[NCH], const int* ltab,
-                                                unsigned char* tile, unsigned* err, int spin_limit, int lane, bool dead,
-                                                int& retries) {
-    u32x4 v[NCH];
-#pragma unroll
-    for (int i = 0; i < NCH; ++i) v[i] = poll_load<FAST>(rs, goff[i]);
-    bool bad = false;
-#pragma unroll
-    for (int i = 0; i < NCH; ++i) bad = bad | has_sent16(v[i]);
-    if (__any(bad) && !dead) {
-        int spins = 0;
-        while (true) {
-#pragma unroll
-            for (int i = 0; i < NCH; ++i)
-                if (has_sent16(v[i])) v[i] = poll_load<FAST>(rs, goff[i]);
-            bad = false;
-#pragma unroll
-            for (int i = 0; i < NCH; ++i) bad = bad | has_sent16(v[i]);
-            ++retries;
-            if (!__any(bad)) break;
-            if (spin_check2(spins, spin_limit, err, lane)) {
-                dead = true;
-                break;
-            }
-        }
-    }
-    int lo[NCH];
-#pragma unroll
-    for (int i = 0; i < NCH; ++i) lo[i] = ltab[i * 512];
-#pragma unroll
-    for (int i = 0; i < NCH; ++i) *reinterpret_cast<u32x4*>(tile + lo[i]) = v[i];
-    return dead;
-}
-
 // ============================================================================
 // forward
 // ============================================================================

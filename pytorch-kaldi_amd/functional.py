@@ -2610,6 +2610,102 @@ class RecLayerPerfFn(torch.autograd.Function):
         return dx, None, (None if side_w else dW), dbias, (None if side_u else dU), dgamma, dbeta, None, None, None, None, None
 
 
+def cudnn_dirs_ok(cell, act, T, B, H):
+    """Whether a torch-layout bidirectional layer (nn._Cudnn) runs as RecLayerDirsFn: PK_EXPERIMENT cudnn_dirs=0 keeps one
+    launch per direction, forced kinks (parity tests) are drawn per single-direction call, and the library has the last
+    word on cell, kernel variant, shape and residency."""
+    if _lib.experiment("cudnn_dirs", "1") == "0" or _Kinks.queue is not None:
+        return False
+    return _lib.load().pk_rec_dirs_covered(CELL[cell], ACT[act], T, B, H) == 1
+
+
+class RecLayerDirsFn(torch.autograd.Function):
+    """One torch-layout bidirectional layer (LSTM_cudnn / RNN_cudnn: a weight set per direction) of the bf16 pipeline,
+    both directions in ONE recurrence launch each way (pk_rec_persist2_dirs.hip):
+
+      y = f(x, W0, b0, U0, W1, b1, U1)      W_d / U_d / b_d: direction d's matrices in the kernels' gate order
+
+    Two projection GEMMs fill the two slabs of P from one bf16 copy of x - the kernels read the reversed direction's slab
+    backwards in time and store its output at the original time index in columns H:2H, so there is no reversed copy of x
+    and no join of two outputs.  Backward: one launch, then per direction dU_d and dW_d from the slabs of dGb (the k-major
+    operands the kernels publish) and one dx GEMM each.  Operands, GEMMs and per-row arithmetic are those of
+    RecLayerPerfFn run once per direction: y and dx are bit-identical to that path; the weight and bias gradients of the
+    reversed direction sum their rows in the opposite time order."""
+
+    @staticmethod
+    def forward(ctx, x, W0, b0, U0, W1, b1, U1, cfg):
+        _need_gpu(x, W0, b0, U0, W1, b1, U1)
+        lib = _lib.load()
+        geom = _rec_geom(lib, cfg, x.shape)
+        T, B, D, TB, GH, H = geom.T, geom.B, geom.D, geom.TB, geom.GH, cfg.H
+        xb = cvt_bf16(_rows2d(x))
+        Wb = [cvt_bf16(W0.contiguous()), cvt_bf16(W1.contiguous())]
+        P = _new(2, TB, GH, like=W0)
+        for d in range(2):
+            gemm_bf16(TB, GH, D, xb, xb.shape[1], 1, Wb[d], Wb[d].shape[1], 1, P[d], GH)
+        pscale = torch.ones(2 * GH, device=x.device)
+        pshift = torch.cat([b.reshape(-1) if b is not None else torch.zeros(GH, device=x.device) for b in (b0, b1)])
+        U2 = torch.stack([U0, U1]).contiguous()
+        Yb = torch.empty(TB, geom.y_pitch, device=x.device, dtype=torch.bfloat16)
+        self_fill = settings.self_fill and lib.pk_rec_self_fill(CELL[cfg.cell]) == 1
+        # (a forward-only chunk saves nothing for a backward pass: S is None, as in RecLayerPerfFn)
+        infer = not any(ctx.needs_input_grad) and _lib.experiment("fwd_nosave", "1") != "0"
+        Y = _new(T, B, 2 * H, like=W0)
+        S = None if infer else _new(2, TB, geom.NS * H, like=W0)
+        _lib.raise_if_persist_failed()
+        _lib.check(lib.pk_rec_fwd_bf16_dirs(_stream(), CELL[cfg.cell], ACT[cfg.act], T, B, 1, H, _p(P), _p(pscale), _p(pshift),
+                                            _p(U2), None, 1.0, _p(Y), _p(S), _p(Yb), geom.y_pitch, 2 if self_fill else 0),
+                   "pk_rec_fwd_bf16_dirs")
+        ctx.save_for_backward(xb, Wb[0], Wb[1], U2, P, Y, S, Yb)
+        ctx.cfg, ctx.geom, ctx.self_fill = cfg, geom, self_fill
+        ctx.has_bias = (b0 is not None, b1 is not None)
+        return Y
+
+    @staticmethod
+    def backward(ctx, dY):
+        lib = _lib.load()
+        xb, Wb0, Wb1, U2, P, Y, S, Yb = ctx.saved_tensors
+        cfg, geom = ctx.cfg, ctx.geom
+        T, B, D, G, TB, GH, Gp, Hp, H = geom.T, geom.B, geom.D, geom.G, geom.TB, geom.GH, geom.g_pitch, geom.Hp, cfg.H
+        dY = dY.contiguous()
+        dGb = torch.empty(2 * TB, Gp, device=dY.device, dtype=torch.bfloat16)
+        flush_deferred_side()
+        _lib.check(lib.pk_rec_bwd_bf16_dirs(_stream(), CELL[cfg.cell], ACT[cfg.act], T, B, 1, H, _p(U2), None, 1.0, _p(Y), _p(S),
+                                            _p(dY), None, _p(dGb), Gp, 2 if ctx.self_fill else 0), "pk_rec_bwd_bf16_dirs")
+        Yp, Kh = Yb.shape[1], (T - 1) * B
+        Mp = GH if Hp == H else G * Hp
+        part = _new(int(lib.pk_bn_partial_floats(TB, GH)), like=dY)
+        dPb = torch.empty(2, TB, _up(GH, 64), device=dY.device, dtype=torch.bfloat16)
+        dx = _new(2 if ctx.needs_input_grad[0] else 0, TB, D, like=dY)
+        grads = []
+        for d, Wb in enumerate((Wb0, Wb1)):
+            # dU_d = sum over the steps whose previous state exists of dgate^T . h_prev: rows ts >= 1 against h at ts - 1
+            # (direction 0), rows ts <= T - 2 against h at ts + 1 (direction 1) - _deferred_dU_bf16's operands, one
+            # direction at a time; with the gates re-pitched to Hp the product has Hp - H dead rows per gate
+            dU = _new(GH, H, like=dY)
+            if Kh == 0:
+                dU.zero_()
+            else:
+                out = dU if Hp == H else _new(Mp, H, like=dY)
+                gemm_bf16(Mp, H, Kh, (dGb, (d * TB + (0 if d else B)) * Gp), Gp, 0, (Yb, (B if d else 0) * Yp + d * Hp), Yp, 0,
+                          out, H, splitk=_splitk_bf(_tiles_bf(Mp, H), Kh))
+                if Hp != H:
+                    for g in range(G):
+                        dU[g * H:(g + 1) * H].copy_(out[g * Hp:g * Hp + H])
+            # the slab of dGb as the bf16 projection gradient, and the bias gradient: its column sums
+            sum_g = _new(GH, like=dY)
+            _lib.check(lib.pk_bn_bwd_bf16(_stream(), ctypes.c_void_p(dGb.data_ptr() + 2 * d * TB * Gp), None, Gp, G, H, _p(P[d]),
+                                          GH, TB, None, None, cfg.eps, None, float(TB), _p(part), _p(sum_g), None, _p(dPb[d]),
+                                          dPb.shape[2], None, None), "pk_bn_bwd_bf16")
+            dW = _new(GH, D, like=dY)
+            gemm_bf16(GH, D, TB, dPb[d], dPb.shape[2], 0, xb, xb.shape[1], 0, dW, D, splitk=_splitk_bf(_tiles_bf(GH, D), TB))
+            if ctx.needs_input_grad[0]:  # dx_d = dP_d . W_d; the two are added as autograd adds the two paths' gradients
+                gemm_bf16(TB, D, GH, dPb[d], dPb.shape[2], 1, Wb, Wb.shape[1], 0, dx[d], D)
+            grads += [dW, sum_g if ctx.has_bias[d] else None, dU]
+        dxs = dx[0].add_(dx[1]).view(T, B, D) if ctx.needs_input_grad[0] else None
+        return (dxs,) + tuple(grads) + (None,)
+
+
 # ----------------------------------------------------------------------------
 # conv1d + max_pool1d (neural_networks.py:1546-1552, 1655-1661, 1805-1813)
 # ----------------------------------------------------------------------------

@@ -26,8 +26,8 @@ it changes ``arch_library`` from ``quaternion_neural_networks``); its initialisa
 as the reference's does.
 
 ``LSTM_cudnn`` / ``RNN_cudnn`` (neural_networks.py:153-203, :256-297) keep torch.nn.LSTM / nn.RNN's parameter names, layout and
-initialisation and run on the LSTM / RNN cells, one direction per launch; ``GRU_cudnn`` raises: nn.GRU's cell is none of the
-engine's.
+initialisation and run on the LSTM / RNN cells - a bidirectional layer in bf16 mode as one launch over both directions with
+a weight set each, otherwise one direction per launch; ``GRU_cudnn`` raises: nn.GRU's cell is none of the engine's.
 
 The nn.Linear / nn.BatchNorm1d / nn.Conv1d sub-modules are parameter containers
 only: ``forward`` never calls them, it hands their tensors to the HIP kernels
@@ -869,7 +869,10 @@ class _Cudnn(_Recurrent):
     (functional.gates_pack); the backward direction runs on the time-reversed input, and functional.seq_join puts the two
     outputs together, applies torch's inter-layer dropout and writes the next layer's reversed input in the same pass.  The
     two directions run one after the other on one stream.  Weight gradients come back through autograd, on the main stream;
-    no bf16 copy is handed from layer to layer (it would have to cross the join)."""
+    no bf16 copy is handed from layer to layer (it would have to cross the join).
+    A bidirectional stack on the bf16 persistent route runs every layer as ONE node instead, both directions in one
+    recurrence launch each way with a weight set per direction (_forward_dirs; PK_EXPERIMENT cudnn_dirs=0 keeps the path
+    above, which also serves fp32 mode, PK_REC_ALGO=stepwise, length-aware batches and unidirectional layers)."""
     KIND = ATTR = None
 
     def _setup(self, options, inp_dim, act):
@@ -934,6 +937,21 @@ class _Cudnn(_Recurrent):
     def _layer_matrices(self, wps, ups, perf, edge):
         return wps[0], ups[0], False, False
 
+    def _forward_dirs(self, x, masks, scale, route):
+        """A bidirectional stack on the bf16 persistent route, no sentence lengths in force: every layer is ONE node
+        (functional.RecLayerDirsFn: two projection GEMMs, one recurrence launch for both directions each way) whose
+        output already is the joined [T, B, 2H] tensor.  No reversed input and no reversed output exist; the inter-layer
+        dropout is the join kernel on that tensor, mask and scale only, and with nothing to drop no launch at all."""
+        H = self.hidden_size
+        base = (self.KIND, self._act[0], H, True, False, self.training, 1e-5, 0.05, 1.0)
+        for k in range(self.num_layers):
+            (W0,), (U0,), b0 = self._layer_params(2 * k)
+            (W1,), (U1,), b1 = self._layer_params(2 * k + 1)
+            x = F_.RecLayerDirsFn.apply(x, W0, b0, U0, W1, b1, U1, F_.RecCfg(*base, route=route))
+            if masks is not None and k < self.num_layers - 1:
+                x = F_.seq_join(x, None, masks[k], scale)[0]
+        return x
+
     def forward(self, x, drop_masks=None):
         if not x.is_cuda:
             raise PkError("pytorch-kaldi_amd.nn.%s runs on the GPU only: set use_cuda=True" % type(self).__name__)
@@ -952,6 +970,9 @@ class _Cudnn(_Recurrent):
             else:
                 masks = self._draw_masks(T, B, x.device)
         route = F_.rec_route(self.KIND, H, False, False, self.training)
+        if (ndir == 2 and lens is None and route.perf and route.family == "bf16"
+                and F_.cudnn_dirs_ok(self.KIND, self._act[0], T, B, H)):
+            return self._forward_dirs(x, masks, scale, route)
         inp_f = x
         if lens is not None:
             inp_b = F_.seq_pack_len(x, lens, want_f=False)[1]

@@ -15,6 +15,11 @@ stack (B rows per launch, weight gradients through autograd): the recurrence lau
 unpack and join.  The pack / unpack and join kernels are also timed on their own (device events, all launches one step
 makes), so that the distance to the partner splits into: second recurrence launch, pack / unpack, join, main-stream weight
 gradients.
+
+"LSTM_cudnn" takes the default path: in bf16 mode both directions of a layer in one recurrence launch
+(pk_rec_persist2_dirs.hip).  "LSTM_cudnn_per_dir" is a second LSTM_cudnn module whose steps run under PK_EXPERIMENT
+cudnn_dirs=0 - one launch per direction and the joins, the path before - in the same process and the same alternating
+windows; `lstm_cudnn_per_dir_over_lstm` is the old ratio measured in the same run.
 """
 import argparse
 import importlib
@@ -34,7 +39,7 @@ OPT = importlib.import_module("pytorch-kaldi_amd.optim")
 
 def build(kind, H, L, D):
     rep = lambda v: ",".join([v] * L)  # noqa: E731
-    if kind == "LSTM_cudnn":
+    if kind in ("LSTM_cudnn", "LSTM_cudnn_per_dir"):
         net = nn_amd.LSTM_cudnn({"hidden_size": str(H), "num_layers": str(L), "bias": "True", "batch_first": "True",
                                  "dropout": "0.2", "bidirectional": "True", "use_cuda": "True", "to_do": "train"}, D)
     else:
@@ -119,11 +124,24 @@ def main():
     if not torch.cuda.is_available():
         sys.exit("time_cudnn_step.py measures on the GPU; none is visible")
     torch.manual_seed(1)
-    models = {k: build(k, a.H, a.L, a.D) for k in ("LSTM_cudnn", "LSTM", "LSTM_autograd", "LSTM_uni_x2")}
+    models = {k: build(k, a.H, a.L, a.D) for k in ("LSTM_cudnn", "LSTM_cudnn_per_dir", "LSTM", "LSTM_autograd", "LSTM_uni_x2")}
     x = torch.randn(a.T, a.B, a.D, device="cuda")
     cot = torch.randn(a.T, a.B, 2 * a.H, device="cuda") / (a.T * a.B)
 
     def step(kind):
+        if kind != "LSTM_cudnn_per_dir":
+            return run_step(kind)
+        old = os.environ.get("PK_EXPERIMENT")  # (the first occurrence of a key wins; the switch is read at every call)
+        os.environ["PK_EXPERIMENT"] = "cudnn_dirs=0" + ("," + old if old else "")
+        try:
+            run_step(kind)
+        finally:
+            if old is None:
+                del os.environ["PK_EXPERIMENT"]
+            else:
+                os.environ["PK_EXPERIMENT"] = old
+
+    def run_step(kind):
         net, opt = models[kind]
         with F_.accumulating_backward():
             opt.zero_grad()
@@ -151,7 +169,7 @@ def main():
                 torch.cuda.synchronize()
                 ms[kind].append(1e3 * (time.perf_counter() - t0) / a.steps)
         out[prec] = {k: {"ms_per_step": statistics.median(v), "min": min(v), "max": max(v)} for k, v in ms.items()}
-        for k in ("LSTM_cudnn", "LSTM_autograd", "LSTM_uni_x2"):
+        for k in ("LSTM_cudnn", "LSTM_cudnn_per_dir", "LSTM_autograd", "LSTM_uni_x2"):
             out[prec][k.lower() + "_over_lstm"] = out[prec][k]["ms_per_step"] / out[prec]["LSTM"]["ms_per_step"]
         print(prec, json.dumps(out[prec]), flush=True)
     F_.set_precision("fp32")
