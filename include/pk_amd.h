@@ -570,6 +570,35 @@ int pk_seq_join_len(void* stream, const float* hf, const float* hb, int64_t ldi,
 int pk_post_normalize(void* stream, const float* x, const int64_t* rows, int64_t R, int64_t n, int64_t C,
                       const void* logprior, void* out, int f64);
 
+/* ---- Simple Recurrent Unit layers (pk_sru.hip; the `sru` package's v2 cell behind neural_networks.py:1973-2020).  The
+ * layer's matrix work is one GEMM, U = x~ . W; these entries are the scan over time that follows it, one thread per
+ * (sentence, direction, unit) column, both directions in one launch.  out = ndir * H, column col = d*H + j:
+ *     f = sigmoid(u1 + v_f c_prev + b_f)     r = sigmoid(u2 + v_r c_prev + b_r)     c = u0 + (c_prev - u0) f
+ *     h = x' + (act(c) m_h - x') r           c_{-1} = 0; direction 1 walks t = T-1 .. 0
+ *   U          [T*B][out*k] fp32, k = 3 or 4 innermost: u_g = U[t*B + b][col*k + g]; 16-byte aligned for k = 4
+ *   x          [T*B][out] or NULL (k = 3 only): x' = scale_x * x;  k = 4: x' = u3;  k = 3 without x: x' = 0
+ *   weight_c   [2*out] = v_f, v_r;  bias [2*out] = b_f, b_r
+ *   mask_h     [B][out] (already scaled) or NULL
+ *   lens       int32 [B] on the device or NULL: sentence b has lens[b] steps (clamped into 0 .. T), direction 1 starts at
+ *              lens[b] - 1, rows behind it are written as zeros.  Forward only: C must be NULL with it.
+ *   Y          [T*B][out];  C [T*B][out]: every c_t, saved for pk_sru_bwd, or NULL (forward only)
+ *   Ym         NULL, or [T*B][out] = Y * mask_next[b][col] (mask_next [B][out], NULL = 1): the next layer's masked input
+ * pk_sru_bwd walks the other way round and recomputes the gates from U and C.  dY / dYm: gradients of Y / Ym (one may be
+ * NULL).  It writes dU OVER U, dx_skip [T*B][out] (k = 3 with x; written, not accumulated) and partial [B][4*out] = the
+ * per-sentence sums of d v_f, d v_r, d b_f, d b_r: pk_colsum over its B rows gives (d weight_c, d bias).
+ * pk_sru_mask: out[t][i] = x[t][i] * mask[i], i < n - the first layer's input mask, and its own backward. */
+#define PK_SRU_ACT_NONE 0
+#define PK_SRU_ACT_TANH 1
+#define PK_SRU_ACT_RELU 2
+#define PK_SRU_ACT_SELU 3
+int pk_sru_fwd(void* stream, int T, int B, int ndir, int H, int k, int act, const float* U, const float* x, float scale_x,
+               const float* weight_c, const float* bias, const float* mask_h, const int32_t* lens, const float* mask_next,
+               float* Y, float* C, float* Ym);
+int pk_sru_bwd(void* stream, int T, int B, int ndir, int H, int k, int act, float* U, const float* C, const float* x,
+               float scale_x, const float* weight_c, const float* bias, const float* mask_h, const float* dY, const float* dYm,
+               const float* mask_next, float* dx_skip, float* partial);
+int pk_sru_mask(void* stream, const float* x, const float* mask, int64_t T, int64_t n, float* out);
+
 /* persistent-recurrence health: number of spin time-outs since the last reset
  * (host-mapped counter, readable without a device sync). */
 unsigned pk_persist_error_count(void);

@@ -20,7 +20,7 @@ ARCH = "gfx950"
 FLAGS = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC"]
 # per-source additions: the packed-fp32 VALU forms (v_pk_add / mul / fma_f32) are kept out of the newer kernels
 NO_PK_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
-EXTRA_FLAGS = {"pk_rec_persist2_dirs.hip": NO_PK_F32}
+EXTRA_FLAGS = {"pk_rec_persist2_dirs.hip": NO_PK_F32, "pk_sru.hip": NO_PK_F32}
 
 
 def _hipcc():

@@ -1822,6 +1822,131 @@ def post_normalize(x, logprior_dev, rows=None, rows_host=None):
     return out
 
 
+# ----------------------------------------------------------------------------
+# Simple Recurrent Unit (csrc/pk_sru.hip): the scan over time behind a layer's one GEMM.  fp32 in every precision mode.
+# ----------------------------------------------------------------------------
+SRU_ACT = {"none": 0, "tanh": 1, "relu": 2, "selu": 3}  # PK_SRU_ACT_*: the scan's own codes, not act_fun's (ACT has no selu)
+
+
+def _sru_geom(U, weight_c, bias, x_skip, bidirectional, act):
+    """(T, B, ndir, H, out, k) of a scan from its operands, checked on the host."""
+    if act not in SRU_ACT:
+        raise _lib.PkError("sru_scan: activation %r (one of %s)" % (act, ", ".join(SRU_ACT)))
+    if U.dim() != 3:
+        raise _lib.PkError("sru_scan: U must be [T, B, out * k] (got %s)" % (tuple(U.shape),))
+    T, B, W = U.shape
+    out, ndir = weight_c.numel() // 2, 2 if bidirectional else 1
+    if out < ndir or out % ndir or weight_c.numel() != 2 * out or bias.numel() != 2 * out or W not in (3 * out, 4 * out):
+        raise _lib.PkError("sru_scan: U %s, weight_c %s and bias %s do not fit %d direction(s) of k = 3 or 4 matrices"
+                           % (tuple(U.shape), tuple(weight_c.shape), tuple(bias.shape), ndir))
+    k = W // out
+    if x_skip is not None and (k != 3 or tuple(x_skip.shape) != (T, B, out)):
+        raise _lib.PkError("sru_scan: a skip source goes with k = 3 and is [T, B, out] (k = %d, got %s)" % (k, tuple(x_skip.shape)))
+    return T, B, ndir, out // ndir, out, k
+
+
+def _sru_fwd(geom, U, x_skip, weight_c, bias, scale_x, act, mask_h, lens_dev, mask_next, save):
+    T, B, ndir, H, out, k = geom
+    for m in (mask_h, mask_next):
+        if m is not None and tuple(m.shape) != (B, out):
+            raise _lib.PkError("sru_scan: a mask is [B, out] = (%d, %d) (got %s)" % (B, out, tuple(m.shape)))
+    Y = _new(T, B, out, like=U)
+    C = _new(T, B, out, like=U) if save else None
+    Ym = _new(T, B, out, like=U) if mask_next is not None else None
+    _lib.check(_lib.load().pk_sru_fwd(_stream(), T, B, ndir, H, k, SRU_ACT[act], _p(U), _p(x_skip), float(scale_x), _p(weight_c),
+                                      _p(bias), _p(mask_h), _p(lens_dev), _p(mask_next), _p(Y), _p(C), _p(Ym)), "pk_sru_fwd")
+    return Y, C, Ym
+
+
+def _contig(t):
+    return None if t is None else t.contiguous()
+
+
+class SruScanFn(torch.autograd.Function):
+    """(Y, Ym) = scan(U, ...): Ym = Y * mask_next is the next layer's masked GEMM input, written by the same launch (None
+    without mask_next).  Backward takes the gradients of both, writes dU OVER U (the buffer is the GEMM's own output and
+    nothing else reads it) and reduces the per-sentence sums of the vector parameters with colsum."""
+
+    @staticmethod
+    def forward(ctx, U, x_skip, weight_c, bias, scale_x, act, mask_h, mask_next, bidirectional):
+        _need_gpu(U, x_skip, weight_c, bias, mask_h, mask_next)
+        geom = _sru_geom(U, weight_c, bias, x_skip, bidirectional, act)
+        U, x_skip, weight_c, bias = U.contiguous(), _contig(x_skip), weight_c.contiguous(), bias.contiguous()
+        mask_h, mask_next = _contig(mask_h), _contig(mask_next)
+        save = any(ctx.needs_input_grad[:4])
+        Y, C, Ym = _sru_fwd(geom, U, x_skip, weight_c, bias, scale_x, act, mask_h, None, mask_next, save)
+        ctx.save_for_backward(U, C, x_skip, weight_c, bias, mask_h, mask_next)
+        ctx.geom, ctx.scale_x, ctx.act = geom, float(scale_x), act
+        ctx.set_materialize_grads(False)
+        return Y, Ym
+
+    @staticmethod
+    def backward(ctx, dY, dYm):
+        U, C, x_skip, weight_c, bias, mask_h, mask_next = ctx.saved_tensors
+        T, B, ndir, H, out, k = ctx.geom
+        if dY is None and dYm is None:
+            return (None,) * 9
+        dY, dYm = _contig(dY), _contig(dYm)
+        dxs = _new(T, B, out, like=U) if x_skip is not None else None
+        part = _new(B, 4 * out, like=U)
+        _lib.check(_lib.load().pk_sru_bwd(_stream(), T, B, ndir, H, k, SRU_ACT[ctx.act], _p(U), _p(C), _p(x_skip), ctx.scale_x,
+                                          _p(weight_c), _p(bias), _p(mask_h), _p(dY), _p(dYm), _p(mask_next), _p(dxs), _p(part)),
+                   "pk_sru_bwd")
+        sums = colsum(part)
+        return (U, dxs, sums[:2 * out].view_as(weight_c), sums[2 * out:].view_as(bias)) + (None,) * 5
+
+
+def sru_scan(U, x_skip, weight_c, bias, scale_x, act, mask_h=None, lens=None, bidirectional=False, mask_next=None):
+    """The SRU recurrence over U [T, B, out * k] = x~ . W (k = 3 or 4 matrices per unit, innermost; out = weight_c.numel() / 2,
+    two directions of out / 2 units with bidirectional) -> Y [T, B, out]; with mask_next [B, out] -> (Y, Y * mask_next).
+
+        f = sigmoid(u1 + v_f c_prev + b_f)   r = sigmoid(u2 + v_r c_prev + b_r)   c = u0 + (c_prev - u0) f
+        h = x' + (act(c) mask_h - x') r      x' = u3 (k = 4) | scale_x * x_skip (k = 3) | 0 (k = 3, x_skip None)
+
+    weight_c = (v_f, v_r), bias = (b_f, b_r), each half [out]; act: a key of SRU_ACT; mask_h [B, out], already scaled.
+    Differentiable in U, x_skip, weight_c and bias.  U IS CONSUMED: backward writes dU over it and returns that buffer.
+    lens (a sentence_lengths, a sequence, or None): forward only - sentence b runs over its own lens[b] steps, direction 1
+    from its last one, and the rows behind it are zeros."""
+    if lens is None:
+        Y, Ym = SruScanFn.apply(U, x_skip, weight_c, bias, scale_x, act, mask_h, mask_next, bidirectional)
+    else:
+        U, x_skip, weight_c, bias = U.detach().contiguous(), _contig(x_skip), weight_c.detach().contiguous(), bias.detach().contiguous()
+        x_skip = None if x_skip is None else x_skip.detach()
+        _need_gpu(U, x_skip, weight_c, bias, mask_h, mask_next)
+        lens = _lens_arg("sru_scan", lens, U)
+        geom = _sru_geom(U, weight_c, bias, x_skip, bidirectional, act)
+        Y, _, Ym = _sru_fwd(geom, U, x_skip, weight_c, bias, scale_x, act, _contig(mask_h), lens.device_tensor(U.device),
+                            _contig(mask_next), False)
+    return Y if mask_next is None else (Y, Ym)
+
+
+class SruMaskFn(torch.autograd.Function):
+    """x [T, B, n] * mask [B, n], the time-constant input mask of the first SRU layer (pk_sru_mask, both ways)."""
+
+    @staticmethod
+    def forward(ctx, x, mask):
+        _need_gpu(x, mask)
+        x, mask = x.contiguous(), mask.contiguous()
+        if x.dim() != 3 or tuple(mask.shape) != tuple(x.shape[1:]):
+            raise _lib.PkError("sru_mask: x [T, B, n] and mask [B, n] (got %s and %s)" % (tuple(x.shape), tuple(mask.shape)))
+        ctx.save_for_backward(mask)
+        out = torch.empty_like(x)
+        _lib.check(_lib.load().pk_sru_mask(_stream(), _p(x), _p(mask), x.shape[0], mask.numel(), _p(out)), "pk_sru_mask")
+        return out
+
+    @staticmethod
+    def backward(ctx, dy):
+        (mask,) = ctx.saved_tensors
+        dy = dy.contiguous()
+        dx = torch.empty_like(dy)
+        _lib.check(_lib.load().pk_sru_mask(_stream(), _p(dy), _p(mask), dy.shape[0], mask.numel(), _p(dx)), "pk_sru_mask")
+        return dx, None
+
+
+def sru_mask(x, mask):
+    return SruMaskFn.apply(x, mask)
+
+
 class LnLastActDropFn(torch.autograd.Function):
     """drop(act(LayerNorm(z))) behind a conv layer's max-pool as ONE launch each way (pk_ln_last_act_drop_*), the CNN /
     SincNet flavour of the reference's LayerNorm (features [C, L], statistics over the last dim:

@@ -29,6 +29,10 @@ as the reference's does.
 initialisation and run on the LSTM / RNN cells - a bidirectional layer in bf16 mode as one launch over both directions with
 a weight set each, otherwise one direction per launch; ``GRU_cudnn`` raises: nn.GRU's cell is none of the engine's.
 
+``SRU`` (neural_networks.py:1973-2020, there a wrapper round the ``sru`` package) is built from the SRU paper and the
+documented behaviour of the package's v2 cell: one GEMM per layer and a fused scan over time (pk_sru.hip).  Parameter names
+and shapes follow the package as far as known; its checkpoints are untested.
+
 The nn.Linear / nn.BatchNorm1d / nn.Conv1d sub-modules are parameter containers
 only: ``forward`` never calls them, it hands their tensors to the HIP kernels
 through ``functional``.  There is no CPU path: ``use_cuda`` must be True.
@@ -1028,6 +1032,145 @@ class GRU_cudnn(nn.Module):
         raise PkError("GRU_cudnn: torch.nn.GRU computes its candidate as n = tanh(W_n x + b_in + r * (U_n h + b_hn)) - the "
                       "reset gate multiplies the recurrent product - which is none of the engine's cells: its GRU cell is the "
                       "reference-form one, tanh(W x + U (r * h)).  Use arch_class = GRU, the class the engine runs.")
+
+
+class _SRUCell(nn.Module):
+    """Parameters of one SRU layer under the `sru` package's names, registered in its order: weight, weight_proj, weight_c,
+    bias (their layout: see SRU)."""
+
+    def __init__(self, n_in, out, k, n_proj, highway_bias):
+        super().__init__()
+        rows = n_proj if n_proj else n_in
+        self.weight = nn.Parameter(torch.empty(rows, out * k).uniform_(-math.sqrt(3.0 / rows), math.sqrt(3.0 / rows)))
+        if n_proj:
+            self.weight_proj = nn.Parameter(torch.empty(n_in, n_proj).uniform_(-math.sqrt(3.0 / n_in), math.sqrt(3.0 / n_in)))
+        else:
+            self.register_parameter("weight_proj", None)
+        self.weight_c = nn.Parameter(torch.empty(2 * out).uniform_(-math.sqrt(3.0), math.sqrt(3.0)) * math.sqrt(0.5))
+        self.bias = nn.Parameter(torch.cat([torch.zeros(out), torch.full((out,), float(highway_bias))]))
+
+
+class _SRUStack(nn.Module):
+    def __init__(self):
+        super().__init__()
+        self.rnn_lst = nn.ModuleList([])
+
+
+class SRU(nn.Module):
+    """neural_networks.py:1973-2020, a wrapper round the `sru` package there.  Here the layers are built from the SRU paper
+    (Lei et al., 2018) and the documented behaviour of the package's v2 cell: one GEMM per layer and the fused time scan of
+    functional.sru_scan (csrc/pk_sru.hip).  Per layer, with out = D * H, n_in = inp_dim or out, k = 4 if has_skip_term and
+    n_in != out else 3:
+
+        weight_proj [n_in, n_proj], weight [n_proj, out * k]     if 0 < n_proj < min(n_in, out), else weight [n_in, out * k]
+        weight_c [2 * out] = v_f, v_r      bias [2 * out] = b_f, b_r      column (d * H + j) * k + g of weight: matrix g
+
+    State-dict names (sru.rnn_lst.{l}.weight, .weight_proj, .weight_c, .bias) and shapes follow the package as far as known;
+    checkpoints of the package itself are untested.  weight_norm and layer_norm are refused."""
+
+    def __init__(self, options, inp_dim):
+        super().__init__()
+        self.input_dim = inp_dim
+        self.hidden_size = int(_opt(options, "sru_hidden_size"))
+        self.num_layers = int(_opt(options, "sru_num_layers"))
+        self.dropout = float(_opt(options, "sru_dropout"))
+        self.rnn_dropout = float(_opt(options, "sru_rnn_dropout"))
+        acts = [a for a in ("tanh", "relu", "selu") if strtobool(_opt(options, "sru_use_" + a))]
+        self.weight_norm = bool(strtobool(_opt(options, "sru_weight_norm")))
+        self.layer_norm = bool(strtobool(_opt(options, "sru_layer_norm")))
+        self.bidirectional = bool(strtobool(_opt(options, "sru_bidirectional")))
+        self.is_input_normalized = bool(strtobool(_opt(options, "sru_is_input_normalized")))  # (initialisation only in the package)
+        self.has_skip_term = bool(strtobool(_opt(options, "sru_has_skip_term")))
+        self.rescale = bool(strtobool(_opt(options, "sru_rescale")))
+        self.highway_bias = float(_opt(options, "sru_highway_bias"))
+        self.n_proj = int(_opt(options, "sru_n_proj"))
+        self.use_cuda = strtobool(_opt(options, "use_cuda"))
+        self.to_do = _opt(options, "to_do")
+        if len(acts) > 1:
+            raise PkError("SRU: more than one of sru_use_tanh / sru_use_relu / sru_use_selu is set (%s)" % ", ".join(acts))
+        if self.weight_norm or self.layer_norm:
+            raise PkError("SRU: sru_weight_norm and sru_layer_norm are not on the engine (the scan kernel has neither)")
+        if not (0.0 <= self.dropout < 1.0 and 0.0 <= self.rnn_dropout < 1.0):
+            raise PkError("SRU: sru_dropout = %g and sru_rnn_dropout = %g must lie in [0, 1)" % (self.dropout, self.rnn_dropout))
+        if self.hidden_size < 1 or self.num_layers < 1 or inp_dim < 1:
+            raise PkError("SRU: sru_hidden_size = %d, sru_num_layers = %d and the input width %d must be positive"
+                          % (self.hidden_size, self.num_layers, inp_dim))
+        self.act = acts[0] if acts else "none"
+        self.scale_x = math.sqrt(1.0 + 2.0 * math.exp(self.highway_bias)) if self.rescale else 1.0
+        out = self.hidden_size * (2 if self.bidirectional else 1)
+        self.out_dim = out
+        self.sru = _SRUStack()
+        self._k, self._skip = [], []
+        n_in = inp_dim
+        for _ in range(self.num_layers):
+            k = 4 if self.has_skip_term and n_in != out else 3
+            n_proj = self.n_proj if 0 < self.n_proj < min(n_in, out) else 0
+            cell = _SRUCell(n_in, out, k, n_proj, self.highway_bias)
+            if self.rescale:
+                with torch.no_grad():
+                    w = cell.weight.view(-1, out, k)
+                    w[:, :, 0].mul_(math.sqrt(1.0 - self.dropout))
+                    w.mul_(math.sqrt(1.0 - self.rnn_dropout))
+                    if k == 4:
+                        w[:, :, 3].mul_(self.scale_x)
+            self.sru.rnn_lst.append(cell)
+            self._k.append(k)
+            self._skip.append(k == 3 and self.has_skip_term)
+            n_in = out
+
+    def pk_unused_parameters(self):
+        return []
+
+    def pk_flat_groups(self):
+        """optim.FlatParams layout: layer by layer, in the order a layer's forward uses them."""
+        out = []
+        for cell in self.sru.rnn_lst:
+            out += [[p] for p in (cell.weight_proj, cell.weight, cell.weight_c, cell.bias) if p is not None]
+        return out
+
+    _lengths_in_force = _Recurrent._lengths_in_force
+
+    def _masks(self, x, drop_masks):
+        """Per layer (m_rnn [B, n_in] or None, m_h [B, out] or None), scaled; no m_h on the last layer."""
+        B, dev, L = x.shape[1], x.device, self.num_layers
+        if drop_masks is not None:
+            return [tuple(None if m is None else m.to(dev).float().contiguous() for m in pair) for pair in drop_masks]
+        masks = []
+        for i in range(L):
+            n_in = self.input_dim if i == 0 else self.out_dim
+            m_rnn = m_h = None
+            if self.training and self.rnn_dropout > 0.0:
+                m_rnn = F_.dropout_mask(torch.empty(B, n_in, device=dev), self.rnn_dropout)
+            if self.training and self.dropout > 0.0 and i < L - 1:
+                m_h = F_.dropout_mask(torch.empty(B, self.out_dim, device=dev), self.dropout)
+            masks.append((m_rnn, m_h))
+        return masks
+
+    def forward(self, x, drop_masks=None):
+        if not x.is_cuda:
+            raise PkError("pytorch-kaldi_amd.nn.SRU runs on the GPU only: set use_cuda=True")
+        lens = self._lengths_in_force(x)
+        T, B = x.shape[0], x.shape[1]
+        masks = self._masks(x, drop_masks)
+        L, out = self.num_layers, self.out_dim
+        if lens is not None:
+            x = x.detach()
+        xm = x if masks[0][0] is None else F_.sru_mask(x, masks[0][0])  # x~ of the first layer; the scan writes the others
+        for i, cell in enumerate(self.sru.rnn_lst):
+            z = xm.reshape(T * B, -1)
+            if cell.weight_proj is not None:
+                z = F_.linear(z, cell.weight_proj.t())
+            U = F_.linear(z, cell.weight.t()).view(T, B, out * self._k[i])
+            m_next = masks[i + 1][0] if i + 1 < L else None
+            if m_next is None and i + 1 < L and self._skip[i + 1] and torch.is_grad_enabled() and lens is None:
+                # the next layer reads y twice (GEMM and skip term): a second copy, so that the two gradients meet inside
+                # the backward scan and not in a stock element-wise add
+                m_next = torch.ones(B, out, device=x.device)
+            res = F_.sru_scan(U, x if self._skip[i] else None, cell.weight_c, cell.bias, self.scale_x, self.act,
+                              mask_h=masks[i][1] if i < L - 1 else None, lens=lens, bidirectional=self.bidirectional,
+                              mask_next=m_next)
+            x, xm = res if m_next is not None else (res, res)
+        return x
 
 
 class SincConv(nn.Module):
