@@ -599,6 +599,32 @@ int pk_sru_bwd(void* stream, int T, int B, int ndir, int H, int k, int act, floa
                const float* mask_next, float* dx_skip, float* partial);
 int pk_sru_mask(void* stream, const float* x, const float* mask, int64_t T, int64_t n, float* out);
 
+/* ---- the fusion layer of the multi-microphone Li-GRU (pk_fusion.hip).  One small weight matrix is applied to each of the M
+ * microphone slices of a feature row, then bias, activation and a sum or mean over the microphones.  The two instances of a
+ * layer (wz, wh) run as one launch on stacked parameters: C = 2*H0 columns, column c belongs to half c / H0.
+ *     pre_m[n][c] = sum_f W[c][f] x[n][m*F + f] + b[c]          P[n][c] = R_m act(pre_m[n][c]),  R = sum or mean (1/M)
+ *   x [N][M*F], W [C][F], b [C], slope [2] (PReLU: one per half; NULL otherwise), P [N][C], all fp32 and dense.
+ *   prec: PK_PREC_BF16 rounds x and W to bf16 (fp32 accumulate), PK_PREC_F32 is exact.
+ * pk_fusion_fwd replaces FusionLinearConv.forward (neural_networks.py:2082-2099: a Conv1d with stride F over a [N, 1, M*F]
+ * view, the activation and the reduction, with its [N, H0, M] intermediate) for both instances of fusionRNN_jit's layer 0
+ * (:806-813).  pk_fusion_bwd replaces what autograd records for the same lines: it recomputes pre_m, forms
+ * g_m = dP * act'(pre_m) (* 1/M for the mean; in bf16 mode dP and g_m take their bf16 values) and writes
+ *     dW [C][F] = sum_n sum_m g_m^T x_m     db [C] = sum g_m     dslope [2] = sum dP min(pre_m, 0) (PReLU, else untouched)
+ *     dx [N][M*F] = g_m W                   (dx NULL: not computed)
+ * Sums over rows go through per-workgroup partials in ws (pk_fusion_ws_floats floats) and one ordered reduce: no atomics,
+ * the same bits on every run.  Both refuse (return 2) M * roundup(F, 16) above PK_FUSION_MAX_WIDTH (bf16) or half of it
+ * (fp32), the row tile that fits the LDS, and F above 128 (the weight fragments a lane keeps in registers). */
+#define PK_FUSION_ACT_TANH 0
+#define PK_FUSION_ACT_RELU 1
+#define PK_FUSION_ACT_LEAKY_RELU 2 /* slope 0.01 */
+#define PK_FUSION_ACT_PRELU 3
+#define PK_FUSION_MAX_WIDTH 480
+int pk_fusion_fwd(void* stream, int prec, int64_t N, int M, int F, int H0, int act, int mean, const float* x, const float* W,
+                  const float* b, const float* slope, float* P);
+int64_t pk_fusion_ws_floats(int64_t N, int M, int F, int H0);
+int pk_fusion_bwd(void* stream, int prec, int64_t N, int M, int F, int H0, int act, int mean, const float* x, const float* W,
+                  const float* b, const float* slope, const float* dP, float* dW, float* db, float* dslope, float* dx, float* ws);
+
 /* persistent-recurrence health: number of spin time-outs since the last reset
  * (host-mapped counter, readable without a device sync). */
 unsigned pk_persist_error_count(void);

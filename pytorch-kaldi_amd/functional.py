@@ -1947,6 +1947,67 @@ def sru_mask(x, mask):
     return SruMaskFn.apply(x, mask)
 
 
+# ----------------------------------------------------------------------------
+# The fusion layer of the multi-microphone Li-GRU (csrc/pk_fusion.hip): one small matrix on every microphone's slice of a
+# feature row, bias, activation, sum or mean over the microphones - both instances of a layer (wz, wh) in one launch.
+# ----------------------------------------------------------------------------
+FUSION_ACT = {"tanh": 0, "relu": 1, "leaky_relu": 2, "prelu": 3}  # PK_FUSION_ACT_*
+
+
+def fusion_act(name):
+    """The activation a fusion layer runs for the cfg string `name`: the reference's chain of ifs ends in tanh, which
+    therefore serves every string it does not know."""
+    return name if name in ("leaky_relu", "prelu", "relu") else "tanh"
+
+
+class FusionProjFn(torch.autograd.Function):
+    """P [N, C] = R_m act(x_m W^T + b) over the M slices x_m = x[:, m*F:(m+1)*F] (pk_fusion_fwd); backward recomputes the
+    pre-activations and gives dx (only when x needs it), dW, db and the two PReLU slope gradients (pk_fusion_bwd)."""
+
+    @staticmethod
+    def forward(ctx, x, W, b, slope, M, act, mean):
+        _need_gpu(x, W, b, slope)
+        x, W, b = x.contiguous(), W.contiguous(), b.contiguous()
+        slope = None if slope is None else slope.contiguous()
+        N, C, F = x.shape[0], W.shape[0], W.shape[1]
+        if x.dim() != 2 or W.dim() != 2 or M < 1 or x.shape[1] != M * F or C % 2 or b.numel() != C:
+            raise _lib.PkError("fusion_proj: x [N, M*F], W [2*H0, F] and b [2*H0] with M = %d (got %s, %s, %s)"
+                               % (M, tuple(x.shape), tuple(W.shape), tuple(b.shape)))
+        if (act == "prelu") != (slope is not None) or (slope is not None and slope.numel() != 2):
+            raise _lib.PkError("fusion_proj: two slopes, one per half, go with prelu and with nothing else")
+        prec = entry_prec()
+        P = _new(N, C, like=x)
+        geom = (prec, N, M, F, C // 2, FUSION_ACT[act], int(mean))
+        _lib.check(_lib.load().pk_fusion_fwd(_stream(), *geom, _p(x), _p(W), _p(b), _p(slope), _p(P)), "pk_fusion_fwd")
+        ctx.save_for_backward(x, W, b, slope)
+        ctx.geom = geom
+        return P
+
+    @staticmethod
+    def backward(ctx, dP):
+        x, W, b, slope = ctx.saved_tensors
+        lib = _lib.load()
+        dP = dP.contiguous()
+        dW, db = torch.empty_like(W), torch.empty_like(b)
+        dslope = None if slope is None else torch.empty_like(slope)
+        dx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
+        ws = _new(int(lib.pk_fusion_ws_floats(*ctx.geom[1:5])), like=x)
+        _lib.check(lib.pk_fusion_bwd(_stream(), *ctx.geom, _p(x), _p(W), _p(b), _p(slope), _p(dP), _p(dW), _p(db), _p(dslope),
+                                     _p(dx), _p(ws)), "pk_fusion_bwd")
+        return dx, dW, db, dslope, None, None, None
+
+
+def fusion_proj(x, W, b, slope, M, act, reduce):
+    """x [N, M*F] -> P [N, 2*H0]: P[n, c] = R_m act(sum_f W[c, f] x[n, m*F + f] + b[c]), the two instances of a fusion layer
+    stacked: W [2*H0, F], b [2*H0], slope [2] (act "prelu": one per half; None otherwise).  act: "tanh", "relu",
+    "leaky_relu" (0.01) or "prelu"; reduce: "mean", anything else sums.  Differentiable in x, W, b and slope.  In bf16 mode
+    x, W and the operands of the gradient products are rounded to bf16; accumulation is fp32.  Refused: more than 128
+    features per microphone, M * roundup(F, 16) above 480 (bf16 mode) / 240 (fp32 modes)."""
+    if act not in FUSION_ACT:
+        raise _lib.PkError("fusion_proj: activation %r (one of %s)" % (act, ", ".join(FUSION_ACT)))
+    return FusionProjFn.apply(x, W, b, slope, int(M), act, reduce == "mean")
+
+
 class LnLastActDropFn(torch.autograd.Function):
     """drop(act(LayerNorm(z))) behind a conv layer's max-pool as ONE launch each way (pk_ln_last_act_drop_*), the CNN /
     SincNet flavour of the reference's LayerNorm (features [C, L], statistics over the last dim:
@@ -2113,11 +2174,12 @@ class RecRoute(NamedTuple):
 _REC_BF16 = {"bf16": "pk_rec_%s_bf16", "bf16_ln": "pk_rec_%s_bf16_ln", "2p_bf16": "pk_rec2p_%s_bf16", "2p_bf16_ln": "pk_rec2p_%s_bf16_ln"}
 
 
-def rec_route(cell, H, use_ln, use_bn, training):
+def rec_route(cell, H, use_ln, use_bn, training, general=False):
     """The node, the algorithm and the entry family of a layer.  The perf node runs persistent kernels only and never
-    asks choose_rec_algo (which raises under a forced "persistent" for the layers of the general node it cannot cover)."""
+    asks choose_rec_algo (which raises under a forced "persistent" for the layers of the general node it cannot cover).
+    general: a layer only the general node can run (precomputed projections) - its route there, in every precision mode."""
     two_phase = cell in ("GRU", "minimalGRU")
-    if perf_path_ok(cell, H, use_ln, use_bn, training):
+    if not general and perf_path_ok(cell, H, use_ln, use_bn, training):
         return RecRoute(True, REC_PERSISTENT, "2p_bf16" if two_phase else "bf16")
     algo = choose_rec_algo(cell, H, use_ln)
     if not bf16_mode() or algo != REC_PERSISTENT:
@@ -2157,6 +2219,9 @@ class RecCfg(NamedTuple):
     affine: tuple = None
     keep_y: bool = True    # perf node, forward-only chunks: False = an inner layer whose fp32 output nobody reads
     route: RecRoute = None
+    # general node: x already IS the projections P [T, B, G*H] (functional.fusion_proj made them): no projection GEMM, no dX /
+    # dW GEMMs, and the gradient of that input is dPraw.  Wcat is None then
+    preproj: bool = False
 
 
 # Sizes of one layer call, computed once in forward and kept as ctx.geom.  G gates, NS saved state slots per step; Hp: H
@@ -2329,6 +2394,8 @@ class RecLayerFn(torch.autograd.Function):
 
     x [T,B,D]; Wcat [G*H, D]; bcat [G*H] or None; Ucat [G*H, H]; gamma/beta
     [G*H] or None (BatchNorm on the projections); mask [R,H] or None.
+    cfg.preproj: x [T,B,G*H] is the projections themselves and Wcat is None; everything behind the projection GEMM runs as
+    usual and x's gradient is the gradient of the raw projections.
     """
 
     @staticmethod
@@ -2339,13 +2406,21 @@ class RecLayerFn(torch.autograd.Function):
         route, H = cfg.route, cfg.H
         T, B, D, TB, GH = geom.T, geom.B, geom.D, geom.TB, geom.GH
         x2 = _rows2d(x)
-        Wcat, Ucat = Wcat.contiguous(), Ucat.contiguous()
-        # K1: input projections for all steps at once, on the NON-duplicated batch (the reversed
-        # half of the reference's cat([x, flip(x)]) is the same rows read backwards in time)
-        P = _new(TB, GH, like=x2)
+        Wcat, Ucat = None if cfg.preproj else Wcat.contiguous(), Ucat.contiguous()
         bf = bf16_mode()
         xb = Wb = None
-        if bf:  # perf mode: bf16 operands (rounded once, kept for backward), fp32 accumulate / P
+        if cfg.preproj:
+            if D != GH or bcat is not None:
+                raise _lib.PkError("recurrent layer: precomputed projections are [T, B, %d] and carry their own bias (got %s)"
+                                   % (GH, tuple(x.shape)))
+            P = x2 = x2.contiguous()
+        else:
+            # K1: input projections for all steps at once, on the NON-duplicated batch (the reversed
+            # half of the reference's cat([x, flip(x)]) is the same rows read backwards in time)
+            P = _new(TB, GH, like=x2)
+        if cfg.preproj:
+            pass
+        elif bf:  # perf mode: bf16 operands (rounded once, kept for backward), fp32 accumulate / P
             xb, Wb = cvt_bf16(x2), cvt_bf16(Wcat)
             gemm_bf16(TB, GH, D, xb, xb.shape[1], 1, Wb, Wb.shape[1], 1, P, GH)
         else:
@@ -2447,7 +2522,7 @@ class RecLayerFn(torch.autograd.Function):
         # a row of 3 x 550 = 1650 floats - the GRU - is laid out at 1652, so that rows start 16-byte aligned and the products
         # take the LDS-DMA form of pk_gemm (libri_gru fp32 143.5 -> 137.1 ms, profiles/r06_fp32_gemm_dma.json)
         ldp = GH
-        if use_bn and not bf and GH % 4 != 0:
+        if use_bn and not bf and GH % 4 != 0 and not cfg.preproj:
             ldp = _up(GH, 4)
         dPraw = _new(TB, ldp, like=dY)
         if use_bn:
@@ -2476,6 +2551,10 @@ class RecLayerFn(torch.autograd.Function):
             if ctx.has_bias:
                 dbias = colsum(dPraw)
         dx = dW = None
+        if cfg.preproj:  # the caller's own node turns dPraw into the gradients of whatever made the projections
+            if cfg.side_u:
+                side_launch(do_dU_f32, (Y, S, dP2, dU), cfg.uparams)
+            return (dPraw.view(T, B, GH), None, dbias, None if cfg.side_u else dU, dgamma, dbeta, None, None, None, dlg, dlb, None)
         dW = _new(GH, D, like=dY)
         if bf:
             xb, Wb = x2, Wcat

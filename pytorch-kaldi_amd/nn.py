@@ -33,6 +33,10 @@ a weight set each, otherwise one direction per launch; ``GRU_cudnn`` raises: nn.
 documented behaviour of the package's v2 cell: one GEMM per layer and a fused scan over time (pk_sru.hip).  Parameter names
 and shapes follow the package as far as known; its checkpoints are untested.
 
+``fusionRNN_jit`` (neural_networks.py:719-995, the class of cfg/DIRHA_baselines/DIRHA_fusionRNN_MFCC_6ch.cfg) is the Li-GRU
+behind a fusion layer that applies one small matrix to every microphone's slice of the input (pk_fusion.hip); names,
+shapes and initial distributions are the reference's, the initial values are not bit-equal.
+
 The nn.Linear / nn.BatchNorm1d / nn.Conv1d sub-modules are parameter containers
 only: ``forward`` never calls them, it hands their tensors to the HIP kernels
 through ``functional``.  There is no CPU path: ``use_cuda`` must be True.
@@ -1170,6 +1174,252 @@ class SRU(nn.Module):
                               mask_h=masks[i][1] if i < L - 1 else None, lens=lens, bidirectional=self.bidirectional,
                               mask_next=m_next)
             x, xm = res if m_next is not None else (res, res)
+        return x
+
+
+class _FusionConv(nn.Module):
+    """Parameters of the reference's Conv1d(1, H0, kernel_size=F, stride=F): weight [H0, 1, F] xavier-normal (fan_in = F,
+    fan_out = H0 * F, as torch counts them for that shape), bias [H0] zeros."""
+
+    def __init__(self, F, H0):
+        super().__init__()
+        self.weight = nn.Parameter(nn.init.xavier_normal_(torch.empty(H0, 1, F)))
+        self.bias = nn.Parameter(torch.zeros(H0))
+
+
+class _Slope(nn.Module):
+    """nn.PReLU()'s one parameter."""
+
+    def __init__(self):
+        super().__init__()
+        self.weight = nn.Parameter(torch.full((1,), 0.25))
+
+
+class _FusionLinearConv(nn.Module):
+    """Parameter holder of one fusion layer (neural_networks.py:2057-2099): conv.weight, conv.bias and, for prelu,
+    act_function.weight.  functional.fusion_proj runs both instances of a layer at once."""
+
+    def __init__(self, F, H0, act):
+        super().__init__()
+        self.conv = _FusionConv(F, H0)
+        if act == "prelu":
+            self.act_function = _Slope()
+
+
+class _FusionCell(nn.Module):
+    """One layer's parameters under the reference's names, in its registration order: wz, wh, u, bn_wh, bn_wz."""
+
+    def __init__(self, n_in, H, fusion_act, M):
+        super().__init__()
+        if fusion_act is not None:
+            self.wz = _FusionLinearConv(n_in // M, H, fusion_act)
+            self.wh = _FusionLinearConv(n_in // M, H, fusion_act)
+        else:
+            self.wz, self.wh = nn.Linear(n_in, H, bias=True), nn.Linear(n_in, H, bias=True)
+            for lin in (self.wz, self.wh):
+                nn.init.xavier_normal_(lin.weight)
+                nn.init.zeros_(lin.bias)
+        self.u = nn.Linear(H, 2 * H, bias=False)
+        nn.init.orthogonal_(self.u.weight)
+        self.bn_wh = nn.BatchNorm1d(H, momentum=0.05)
+        self.bn_wz = nn.BatchNorm1d(H, momentum=0.05)
+
+
+class _BnBehindBias:
+    """What _Recurrent._layer reads of a BatchNorm module, for a projection whose nn.Linear has a bias IN FRONT of the
+    normalisation (layers 1 and up of fusionRNN_jit).  Training mode: the batch mean takes the bias out again, so the
+    module's own tensors are handed over and fusionRNN_jit adds the bias to the running mean afterwards.  Otherwise
+    bn(P + b) = (P - (running_mean - b)) * k + beta with k = gamma / sqrt(running_var + eps): the shifted mean, and - with
+    autograd on - a term of value zero on beta that carries the bias's gradient k * d beta."""
+
+    def __init__(self, bn, lin_bias, training):
+        self.weight, self.bias, self.running_mean = bn.weight, bn.bias, bn.running_mean
+        self.running_var, self.num_batches_tracked = bn.running_var, bn.num_batches_tracked
+        if not training:
+            self.running_mean = bn.running_mean - lin_bias.detach()
+            if torch.is_grad_enabled() and lin_bias.requires_grad:
+                k = (bn.weight * torch.rsqrt(bn.running_var + bn.eps)).detach()
+                self.bias = bn.bias + (lin_bias - lin_bias.detach()) * k
+
+
+class _ZeroGradEdge(torch.autograd.Function):
+    """y, unchanged, with an autograd edge to parameters whose gradient is identically zero: the biases in front of a
+    training-mode BatchNorm (their true gradient, the column sum of the normalisation's input gradient, is zero up to
+    rounding).  They get a .grad like every other parameter: optimizers and gradient reductions see the whole set."""
+
+    @staticmethod
+    def forward(ctx, y, *params):
+        ctx.save_for_backward(*params)
+        return y.view_as(y)
+
+    @staticmethod
+    def backward(ctx, dy):
+        return (dy,) + tuple(torch.zeros_like(q) for q in ctx.saved_tensors)
+
+
+class fusionRNN_jit(_Recurrent):
+    """neural_networks.py:719-995 on top of FusionLinearConv (:2057-2099): a bidirectional Li-GRU stack (ReLU candidate,
+    BatchNorm on both projections, one drop mask per call) whose first layer applies one small matrix to each of the M
+    microphones' slices of the feature vector, then bias, activation and a sum or mean over the microphones
+    (functional.fusion_proj, csrc/pk_fusion.hip: both instances in one launch, no [N, H0, M] intermediate).  The recurrences
+    are the Li-GRU's own.  As in the reference: only the first entries of fusionRNN_lay / fusionRNN_drop count (the layer
+    count is the list's length), the stack is bidirectional and the candidate ReLU whatever fusionRNN_bidir /
+    fusionRNN_act say, layer 0 fuses whatever fusionRNN_do_fusion says and is fusion_layer_size // number_of_mic wide,
+    every activation string other than leaky_relu / prelu / relu means tanh, fusion_reduce other than "mean" sums, and the
+    drop mask is scaled by 1 / (1 - p) in training mode and the scalar 1.0 otherwise.
+
+    State-dict names, shapes and registration order are the reference's (model.{i}.wz.conv.weight, ..., model.{i}.u.weight
+    [2H, H] with uz first, model.{i}.bn_wh.*, model.{i}.bn_wz.*), and the initial values come from the same distributions
+    (xavier-normal, zeros, orthogonal, 0.25).  They are NOT claimed to be bit-equal to the reference's for a given seed:
+    its class creates its tensors on a hard-coded "cuda" device, whose generator this one does not follow.
+
+    Length-aware decoding batches (functional.sentence_lengths) are refused; one sentence at a time decodes as usual."""
+    KIND = "liGRU"
+
+    def __init__(self, options, inp_dim):
+        nn.Module.__init__(self)
+        self._pre = "fusionRNN"
+        self._gates = [("wz", "uz", "bn_wz"), ("wh", "uh", "bn_wh")]
+        self.input_dim = inp_dim
+        lay = _ints(_opt(options, "fusionRNN_lay"))
+        drop = _floats(_opt(options, "fusionRNN_drop"))
+        self.number_of_mic = M = int(_opt(options, "fusionRNN_number_of_mic"))
+        self.fusion_layer_size = int(_opt(options, "fusionRNN_fusion_layer_size"))
+        self.fusion_act = F_.fusion_act(str(_opt(options, "fusionRNN_fusion_act")).strip())
+        self.fusion_reduce = str(_opt(options, "fusionRNN_fusion_reduce")).strip()
+        for key in ("fusionRNN_bidir", "fusionRNN_act", "fusionRNN_do_fusion"):  # read and, like the reference, not followed
+            _opt(options, key)
+        self.use_cuda = strtobool(_opt(options, "use_cuda"))
+        self.to_do = _opt(options, "to_do")
+        self.test_flag = self.to_do != "train"
+        if M < 1:
+            raise PkError("fusionRNN_jit: fusionRNN_number_of_mic = %d must be at least 1" % M)
+        if inp_dim < 1 or inp_dim % M != 0:
+            raise PkError("fusionRNN_jit: the input width %d is no multiple of fusionRNN_number_of_mic = %d" % (inp_dim, M))
+        H, H0, L = lay[0], self.fusion_layer_size // M, len(lay)
+        if H0 < 1 or H < 1:
+            raise PkError("fusionRNN_jit: fusionRNN_fusion_layer_size = %d over %d microphones and fusionRNN_lay = %d must "
+                          "give layers at least 1 wide" % (self.fusion_layer_size, M, H))
+        if L == 1 and H0 != H:
+            raise PkError("fusionRNN_jit: with one layer, fusionRNN_fusion_layer_size // fusionRNN_number_of_mic = %d must equal "
+                          "fusionRNN_lay = %d (out_dim is 2 * fusionRNN_lay)" % (H0, H))
+        if not 0.0 <= drop[0] < 1.0:
+            raise PkError("fusionRNN_jit: fusionRNN_drop = %g must lie in [0, 1)" % drop[0])
+        self.fusionRNN_lay = lay
+        self.bidir = 1
+        self._n_lay = L
+        self._lay = [H0] + [H] * (L - 1)
+        self._drop = [drop[0]] * L
+        self._act = ["relu"] * L
+        self._use_bn, self._use_ln = [1] * L, [0] * L
+        self._use_bn_inp = self._use_ln_inp = 0
+        self.model = nn.ModuleList([])
+        cur = inp_dim
+        for i in range(L):
+            self.model.append(_FusionCell(cur, self._lay[i], self.fusion_act if i == 0 else None, M))
+            cur = 2 * self._lay[i]
+        self.out_dim = 2 * H
+
+    # _Recurrent._layer finds a layer's BatchNorm modules as getattr(self, name)[i]
+    def _bn(self, name):
+        lin = {"bn_wz": "wz", "bn_wh": "wh"}[name]
+        return [getattr(c, name) if i == 0 else _BnBehindBias(getattr(c, name), getattr(c, lin).bias, self.training)
+                for i, c in enumerate(self.model)]
+
+    bn_wz = property(lambda self: self._bn("bn_wz"))
+    bn_wh = property(lambda self: self._bn("bn_wh"))
+
+    def pk_unused_parameters(self):
+        return []
+
+    def pk_flat_groups(self):
+        """optim.FlatParams layout: layer by layer, the two instances of every kind back to back in gate order (z, h)."""
+        out = []
+        for i, c in enumerate(self.model):
+            if i == 0:
+                out += [[c.wz.conv.weight, c.wh.conv.weight], [c.wz.conv.bias, c.wh.conv.bias]]
+                if self.fusion_act == "prelu":
+                    out.append([c.wz.act_function.weight, c.wh.act_function.weight])
+            else:
+                out += [[c.wz.weight, c.wh.weight], [c.wz.bias, c.wh.bias]]
+            out += [[c.u.weight], [c.bn_wz.weight, c.bn_wh.weight], [c.bn_wz.bias, c.bn_wh.bias]]
+        return out
+
+    def _layer_params(self, i):
+        c = self.model[i]
+        return [c.wz.weight, c.wh.weight], [c.u.weight], None
+
+    def _layer_matrices(self, wps, ups, perf, edge):
+        # u.weight [2H, H] IS the recurrent matrix in the kernels' gate order (z, h): uz, uh = u(h).chunk(2, 1).  One
+        # parameter holds two gates, so the weight gradients come back through autograd, not from the side stream
+        return torch.cat(wps, 0), ups[0], False, False
+
+    def _drop_mask(self, i, batch, device):
+        p = self._drop[i]
+        if not self.training or p <= 0.0:
+            return None, 1.0
+        return F_.dropout_mask(torch.empty(2 * batch, self._lay[i], device=device), p), 1.0
+
+    def _fusion_layer(self, x, mask, scalar, route):
+        """Layer 0: the fused projection, then the general recurrent node on precomputed projections."""
+        c, H0 = self.model[0], self._lay[0]
+        T, B, D = x.shape
+        F = D // self.number_of_mic
+        W = torch.cat([c.wz.conv.weight.view(H0, F), c.wh.conv.weight.view(H0, F)], 0)
+        b = torch.cat([c.wz.conv.bias, c.wh.conv.bias], 0)
+        slope = None
+        if self.fusion_act == "prelu":
+            slope = torch.cat([c.wz.act_function.weight, c.wh.act_function.weight], 0)
+        P = F_.fusion_proj(x.reshape(T * B, D), W, b, slope, self.number_of_mic, self.fusion_act, self.fusion_reduce)
+        bns = [c.bn_wz, c.bn_wh]
+        gamma, beta = torch.cat([q.weight for q in bns], 0), torch.cat([q.bias for q in bns], 0)
+        rmean = rvar = None
+        if not self.training:
+            rmean, rvar = torch.cat([q.running_mean for q in bns], 0), torch.cat([q.running_var for q in bns], 0)
+        cfg = F_.RecCfg("liGRU", "relu", H0, True, True, self.training, 1e-5, 0.05, scalar, uparams=[c.u.weight], route=route,
+                        preproj=True)
+        y, bmean, bvar = F_.RecLayerFn.apply(P.view(T, B, 2 * H0), None, None, c.u.weight, gamma, beta, rmean, rvar, mask,
+                                             None, None, cfg)
+        if self.training:
+            n = 2 * T * B
+            with torch.no_grad():  # BatchNorm1d(momentum=0.05) over the reference's 2*T*B rows, as in _Recurrent._layer
+                means, vars_ = [q.running_mean for q in bns], [q.running_var for q in bns]
+                torch._foreach_mul_(means + vars_, 0.95)
+                torch._foreach_add_(means, [bmean[:H0], bmean[H0:]], alpha=0.05)
+                torch._foreach_add_(vars_, [bvar[:H0], bvar[H0:]], alpha=0.05 * n / (n - 1))
+                torch._foreach_add_([q.num_batches_tracked for q in bns], 1)
+        return y
+
+    def forward(self, x, drop_masks=None):
+        if not x.is_cuda:
+            raise PkError("pytorch-kaldi_amd.nn.fusionRNN_jit runs on the GPU only: set use_cuda=True")
+        if F_.current_lengths() is not None:
+            raise PkError("fusionRNN_jit: length-aware batches (functional.sentence_lengths) are not covered: the fusion "
+                          "layer has no per-sentence form; decode one sentence at a time")
+        if x.dim() != 3 or x.shape[2] != self.input_dim:
+            raise PkError("fusionRNN_jit: input [T, B, %d] (got %s)" % (self.input_dim, tuple(x.shape)))
+        masks = scalars = None
+        if drop_masks is not None:  # injected: tensors [2B, H_i], already scaled, or 1-element tensors (the scalar)
+            masks = [m.to(x.device).float().contiguous() if m.numel() > 1 else None for m in drop_masks]
+            scalars = [1.0 if m.numel() > 1 else float(m) for m in drop_masks]
+        batch = x.shape[1]
+        routes = [F_.rec_route("liGRU", self._lay[i], False, True, self.training, general=i == 0) for i in range(self._n_lay)]
+        xb = xseg = None
+        for i, route in enumerate(routes):
+            mask_i, scalar_i = (masks[i], scalars[i]) if masks is not None else self._drop_mask(i, batch, x.device)
+            if i == 0:
+                x = self._fusion_layer(x, mask_i, scalar_i, route)
+                continue
+            x, xb, xseg = self._layer(i, x, xb, xseg, mask_i, scalar_i, route, F_.rec_keep_y(routes, i, torch.is_grad_enabled()))
+            if self.training:
+                c = self.model[i]
+                with torch.no_grad():  # the bias in front of BatchNorm: part of the mean the running statistics track
+                    torch._foreach_add_([c.bn_wz.running_mean, c.bn_wh.running_mean], [c.wz.bias.detach(), c.wh.bias.detach()],
+                                        alpha=0.05)
+                if torch.is_grad_enabled() and x.requires_grad:
+                    x = _ZeroGradEdge.apply(x, c.wz.bias, c.wh.bias)
+        if xb is not None:
+            x._pk_twin = (xb, xseg, x._version)
         return x
 
 
