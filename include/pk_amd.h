@@ -625,6 +625,25 @@ int64_t pk_fusion_ws_floats(int64_t N, int M, int F, int H0);
 int pk_fusion_bwd(void* stream, int prec, int64_t N, int M, int F, int H0, int act, int mean, const float* x, const float* W,
                   const float* b, const float* slope, const float* dP, float* dW, float* db, float* dslope, float* dx, float* ws);
 
+/* ---- the raw-audio front-end (pk_logmel.hip).
+ * pk_logmel_fwd replaces logMelFb.forward (neural_networks.py:677-699: torch.stft, pow, sum, two transposes, the filterbank
+ * matmul, max and log10, with [B, ws/2+1, frames, 2] intermediates) by one launch:
+ *     re, im [f][b][k] = sum_n x[f*hop + n][b] * basis[n][k]        frames = 1 + (T - ws) / hop, k < n_freq = ws/2 + 1
+ *     y[f][b][m] = log10(max(sum_k fb[k][m] * (re^2 + im^2), 1e-20))
+ *   x [T][B] (samples of one sentence are B floats apart), fb [n_freq][n_mels], y [frames][B][n_mels], all fp32 and dense.
+ *   basis [Kp][NFT*32], Kp = roundup(ws, 16), NFT = ceil(n_freq / 16): column ft*32 + 2*j + c holds, for frequency
+ *   f = ft*16 + j,  c = 0: w[n] cos(2 pi f n / ws),  c = 1: -w[n] sin(2 pi f n / ws)  (w: the window); rows n >= ws and
+ *   frequencies >= n_freq are zero.  Both products run on the exact-fp32 matrix instruction in every precision mode.
+ *   Covered: 4 <= ws <= 1024, 1 <= hop <= ws, 1 <= n_mels <= 128, T >= ws, B <= 2^19, T*B <= 2^40; anything else returns 2.
+ *   Forward only: the front-end has no parameters and the recipes feed it data.
+ * pk_chavg_fwd replaces channel_averaging.forward (:714-717, an einsum over the microphones):  y[n] = sum_c x[n][c] w[c],
+ * x [N][C], w [C], y [N].  pk_chavg_bwd is what autograd records for it:  dx[n][c] = dy[n] w[c].  C <= PK_CHAVG_MAX_C. */
+#define PK_CHAVG_MAX_C 32
+int pk_logmel_fwd(void* stream, const float* x, const float* basis, const float* fb, int64_t T, int B, int ws, int hop, int n_mels,
+                  float* y);
+int pk_chavg_fwd(void* stream, const float* x, const float* w, int64_t N, int C, float* y);
+int pk_chavg_bwd(void* stream, const float* dy, const float* w, int64_t N, int C, float* dx);
+
 /* persistent-recurrence health: number of spin time-outs since the last reset
  * (host-mapped counter, readable without a device sync). */
 unsigned pk_persist_error_count(void);

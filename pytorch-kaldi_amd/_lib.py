@@ -150,6 +150,9 @@ SIGNATURES = {
     "pk_fusion_fwd": (c_int, [P, c_int, c_int64, c_int, c_int, c_int, c_int, c_int, P, P, P, P, P]),
     "pk_fusion_ws_floats": (c_int64, [c_int64, c_int, c_int, c_int]),
     "pk_fusion_bwd": (c_int, [P, c_int, c_int64, c_int, c_int, c_int, c_int, c_int, P, P, P, P, P, P, P, P, P, P]),
+    "pk_logmel_fwd": (c_int, [P, P, P, P, c_int64, c_int, c_int, c_int, c_int, P]),
+    "pk_chavg_fwd": (c_int, [P, P, P, c_int64, c_int, P]),
+    "pk_chavg_bwd": (c_int, [P, P, P, c_int64, c_int, P]),
     "pk_persist_error_count": (ctypes.c_uint, []),
     "pk_persist_error_reset": (None, []),
     "pk_linear_bn_act_bf16_covers": (c_int, [c_int64, c_int64, c_int64]),

@@ -6,6 +6,7 @@ HIP stream to ``include/pk_amd.h`` entry points.  There is deliberately no
 torch-op fallback: a CPU tensor or a missing library raises.
 """
 import ctypes
+import math
 import os
 import weakref
 from typing import NamedTuple
@@ -2006,6 +2007,91 @@ def fusion_proj(x, W, b, slope, M, act, reduce):
     if act not in FUSION_ACT:
         raise _lib.PkError("fusion_proj: activation %r (one of %s)" % (act, ", ".join(FUSION_ACT)))
     return FusionProjFn.apply(x, W, b, slope, int(M), act, reduce == "mean")
+
+
+# ----------------------------------------------------------------------------
+# The raw-audio front-end (csrc/pk_logmel.hip): framing, window, one-sided DFT, power, mel filterbank and log10 in one launch;
+# the weighted mean over microphones in front of it.
+# ----------------------------------------------------------------------------
+def logmel_basis(ws, window=None):
+    """The windowed one-sided DFT basis of pk_logmel_fwd in the layout its kernel streams, computed in float64: [Kp, NFT*32]
+    fp32, Kp = roundup(ws, 16), NFT = ceil((ws//2 + 1) / 16); column ft*32 + 2*j + c is component c (0: w cos, 1: -w sin) of
+    frequency ft*16 + j.  Rows >= ws and frequencies > ws//2 are zero.  window: [ws], default torch.hann_window (periodic)."""
+    n_freq = ws // 2 + 1
+    Kp, nft = -(-ws // 16) * 16, -(-n_freq // 16)
+    w = torch.hann_window(ws, dtype=torch.float64) if window is None else window.double().cpu()
+    n = torch.arange(ws, dtype=torch.float64)
+    ang = 2.0 * math.pi * ((n[:, None] * torch.arange(n_freq, dtype=torch.float64)[None, :]) % ws) / ws  # (exact integer n*f mod ws)
+    out = torch.zeros(Kp, nft * 16, 2, dtype=torch.float64)
+    out[:ws, :n_freq, 0] = w[:, None] * torch.cos(ang)
+    out[:ws, :n_freq, 1] = -w[:, None] * torch.sin(ang)
+    return out.view(Kp, nft * 32).float()
+
+
+def mel_fbanks(sample_rate, n_freq, n_mels):
+    """[n_freq, n_mels] float64 triangular mel filters: torchaudio's melscale_fbanks with f_min = 0, f_max = float(sr // 2),
+    norm = None, mel_scale = "htk" (written from the formula; unverified against a torchaudio install)."""
+    f_max = float(sample_rate // 2)
+    all_freqs = torch.linspace(0, sample_rate // 2, n_freq, dtype=torch.float64)
+    m_pts = torch.linspace(0.0, 2595.0 * math.log10(1.0 + f_max / 700.0), n_mels + 2, dtype=torch.float64)
+    f_pts = 700.0 * (10.0 ** (m_pts / 2595.0) - 1.0)
+    f_diff = f_pts[1:] - f_pts[:-1]
+    slopes = f_pts[None, :] - all_freqs[:, None]  # [n_freq, n_mels + 2]
+    down = -slopes[:, :-2] / f_diff[:-1]
+    up = slopes[:, 2:] / f_diff[1:]
+    return torch.clamp(torch.min(down, up), min=0.0)
+
+
+def log_mel_fb(x, basis, fb, ws, hop):
+    """x [T, B] (or [T, B, 1]) -> [frames, B, n_mels], frames = 1 + (T - ws) // hop:
+    log10(max(|DFT(w * frame)|^2 @ fb, 1e-20)) as one launch (pk_logmel_fwd).  basis: logmel_basis(ws) on the device;
+    fb [ws//2 + 1, n_mels].  Forward only.  Refused: ws outside 4..1024, hop outside 1..ws, more than 128 filters, T < ws."""
+    if x.dim() == 3 and x.shape[2] == 1:
+        x = x[:, :, 0]
+    _need_gpu(x, basis, fb)
+    if x.requires_grad and torch.is_grad_enabled():
+        raise _lib.PkError("log_mel_fb: forward only - the front-end has no parameters and its input is data (the input "
+                           "requires grad and autograd is on)")
+    ws, hop = int(ws), int(hop)
+    n_freq = ws // 2 + 1
+    if x.dim() != 2 or fb.dim() != 2 or fb.shape[0] != n_freq or tuple(basis.shape) != (-(-ws // 16) * 16, -(-n_freq // 16) * 32):
+        raise _lib.PkError("log_mel_fb: x [T, B], basis = logmel_basis(%d) and fb [%d, n_mels] (got %s, %s, %s)"
+                           % (ws, n_freq, tuple(x.shape), tuple(basis.shape), tuple(fb.shape)))
+    x, basis, fb = x.contiguous(), basis.contiguous(), fb.contiguous()
+    T, B, n_mels = x.shape[0], x.shape[1], fb.shape[1]
+    frames = 1 + (T - ws) // hop if T >= ws and hop >= 1 else 0
+    y = _new(max(frames, 0), B, n_mels, like=x)
+    _lib.check(_lib.load().pk_logmel_fwd(_stream(), _p(x), _p(basis), _p(fb), T, B, ws, hop, n_mels, _p(y)), "pk_logmel_fwd")
+    return y
+
+
+class ChannelAverageFn(torch.autograd.Function):
+    """y[..., 0] = sum_c x[..., c] w[c] (pk_chavg_fwd); backward dx[..., c] = dy w[c] (pk_chavg_bwd).  w is a constant."""
+
+    @staticmethod
+    def forward(ctx, x, w):
+        _need_gpu(x, w)
+        x, w = x.contiguous(), w.contiguous()
+        C = x.shape[-1] if x.dim() >= 1 else 0
+        if x.dim() < 1 or w.dim() != 1 or w.numel() != C or x.numel() == 0:
+            raise _lib.PkError("channel_average: x [..., C] and w [C] (got %s and %s)" % (tuple(x.shape), tuple(w.shape)))
+        y = _new(*x.shape[:-1], 1, like=x)
+        _lib.check(_lib.load().pk_chavg_fwd(_stream(), _p(x), _p(w), x.numel() // C, C, _p(y)), "pk_chavg_fwd")
+        ctx.save_for_backward(w)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        (w,) = ctx.saved_tensors
+        dy = dy.contiguous()
+        dx = _new(*dy.shape[:-1], w.numel(), like=dy)
+        _lib.check(_lib.load().pk_chavg_bwd(_stream(), _p(dy), _p(w), dy.numel(), w.numel(), _p(dx)), "pk_chavg_bwd")
+        return dx, None
+
+
+def channel_average(x, w):
+    """x [..., C], w [C] -> [..., 1]: the weighted sum over the last dimension.  Differentiable in x; at most 32 channels."""
+    return ChannelAverageFn.apply(x, w)
 
 
 class LnLastActDropFn(torch.autograd.Function):

@@ -37,6 +37,10 @@ and shapes follow the package as far as known; its checkpoints are untested.
 behind a fusion layer that applies one small matrix to every microphone's slice of the input (pk_fusion.hip); names,
 shapes and initial distributions are the reference's, the initial values are not bit-equal.
 
+``channel_averaging`` and ``logMelFb`` (neural_networks.py:702-717, :658-699) are the raw-audio front-end: the weighted mean
+over the microphones, then framing, Hann window, DFT, power, mel filterbank and log10 as one launch (pk_logmel.hip).  The
+filterbank is built from torchaudio's formula, not on the package; parity with a torchaudio install is unverified.
+
 The nn.Linear / nn.BatchNorm1d / nn.Conv1d sub-modules are parameter containers
 only: ``forward`` never calls them, it hands their tensors to the HIP kernels
 through ``functional``.  There is no CPU path: ``use_cuda`` must be True.
@@ -1421,6 +1425,80 @@ class fusionRNN_jit(_Recurrent):
         if xb is not None:
             x._pk_twin = (xb, xseg, x._version)
         return x
+
+
+class logMelFb(nn.Module):
+    """neural_networks.py:658-699, there torchaudio's MelSpectrogram pieces round torch.stft.  Here one launch
+    (functional.log_mel_fb, csrc/pk_logmel.hip): [T, B, 1] samples -> [frames, B, logmelfb_nr_filt] log10 mel energies,
+    frames = 1 + (T - window) // shift, periodic Hann window, no centring, power spectrum, floor 1e-20.  The filterbank is
+    built from torchaudio's melscale_fbanks formula (functional.mel_fbanks: f_min = 0, f_max = sr // 2, htk scale, no
+    normalisation); parity with a torchaudio install is unverified.  No parameters: basis and filterbank are non-persistent
+    buffers, the state dict is empty as the reference's.  Forward only; length-aware batches are refused."""
+
+    def __init__(self, options, inp_dim):
+        super().__init__()
+        self._sample_rate = int(_opt(options, "logmelfb_nr_sample_rate"))
+        self._nr_of_filters = int(_opt(options, "logmelfb_nr_filt"))
+        self._stft_window_size = int(_opt(options, "logmelfb_stft_window_size"))
+        self._stft_window_shift = int(_opt(options, "logmelfb_stft_window_shift"))
+        self._use_cuda = strtobool(_opt(options, "use_cuda"))
+        ws, hop, n = self._stft_window_size, self._stft_window_shift, self._nr_of_filters
+        if not (4 <= ws <= 1024 and 1 <= hop <= ws and 1 <= n <= 128 and self._sample_rate >= 2):
+            raise PkError("logMelFb: logmelfb_stft_window_size = %d (4 .. 1024), logmelfb_stft_window_shift = %d (1 .. the "
+                          "window size), logmelfb_nr_filt = %d (1 .. 128), logmelfb_nr_sample_rate = %d (at least 2)"
+                          % (ws, hop, n, self._sample_rate))
+        self.out_dim = n
+        self.register_buffer("basis", F_.logmel_basis(ws), persistent=False)
+        self.register_buffer("fb", F_.mel_fbanks(self._sample_rate, ws // 2 + 1, n).float(), persistent=False)
+
+    def pk_unused_parameters(self):
+        return []
+
+    def pk_flat_groups(self):
+        return []
+
+    def forward(self, x):
+        if x.shape[-1] != 1:
+            raise PkError("Multi channel time signal processing not suppored yet")
+        if not x.is_cuda:
+            raise PkError("pytorch-kaldi_amd.nn.logMelFb runs on the GPU only: set use_cuda=True")
+        if F_.current_lengths() is not None:
+            raise PkError("logMelFb: length-aware batches (functional.sentence_lengths) are not covered: frames of the "
+                          "padding would count as speech; decode one sentence at a time")
+        if x.dim() != 3:
+            raise PkError("logMelFb: input [T, B, 1] (got %s)" % (tuple(x.shape),))
+        return F_.log_mel_fb(x, self.basis, self.fb, self._stft_window_size, self._stft_window_shift)
+
+
+class channel_averaging(nn.Module):
+    """neural_networks.py:702-717: [T, B, C] -> [T, B, 1], the mean over the microphones with the weights
+    chAvg_channelWeights / their sum (float32, as there), functional.channel_average.  No parameters."""
+
+    def __init__(self, options, inp_dim):
+        super().__init__()
+        self._use_cuda = strtobool(_opt(options, "use_cuda"))
+        channel_weights = _floats(_opt(options, "chAvg_channelWeights"))
+        self._nr_of_channels = len(channel_weights)
+        if not 1 <= self._nr_of_channels <= 32 or np.sum(channel_weights) == 0.0:
+            raise PkError("channel_averaging: chAvg_channelWeights names %d channels (1 .. 32) with sum %g (not 0)"
+                          % (self._nr_of_channels, np.sum(channel_weights)))
+        # float32 / float32, what the reference's expression gives under numpy's value-based casting
+        numpy_weights = np.asarray(channel_weights, dtype=np.float32) / np.float32(np.sum(channel_weights))
+        self.register_buffer("_weights", torch.from_numpy(numpy_weights), persistent=False)
+        self.out_dim = 1
+
+    def pk_unused_parameters(self):
+        return []
+
+    def pk_flat_groups(self):
+        return []
+
+    def forward(self, x):
+        if self._nr_of_channels != x.shape[-1]:
+            raise PkError("channel_averaging: %d channel weights for an input of %d channels" % (self._nr_of_channels, x.shape[-1]))
+        if not x.is_cuda:
+            raise PkError("pytorch-kaldi_amd.nn.channel_averaging runs on the GPU only: set use_cuda=True")
+        return F_.channel_average(x, self._weights)
 
 
 class SincConv(nn.Module):
