@@ -644,6 +644,30 @@ int pk_logmel_fwd(void* stream, const float* x, const float* basis, const float*
 int pk_chavg_fwd(void* stream, const float* x, const float* w, int64_t N, int C, float* y);
 int pk_chavg_bwd(void* stream, const float* dy, const float* w, int64_t N, int C, float* dx);
 
+/* ---- SincConv_fast (pk_sincfast.hip; neural_networks.py:1816-1959): C symmetric band-pass filters of K (odd) taps on ONE
+ * input channel, with stride s, zero padding p and dilation d like nn.Conv1d.  h = (K-1)/2;
+ *     y[b][c][t] = x[b][t*s + h*d - p] + sum_(j<h) left[c][j] * (x[b][t*s + j*d - p] + x[b][t*s + (K-1-j)*d - p])
+ *   x [B][n], y / dy [B][C][L_out], L_out = (n + 2p - d(K-1) - 1) / s + 1, all fp32 and dense, in every precision mode.
+ * pk_sincfast_bank replaces :1931-1947 (abs, clamp, two outer products, sin, div, window, cat, flip, the division by
+ *   2*band): left [C][h] only - the right half is its mirror, the centre tap is 1 - in one launch, operation by operation
+ *   in fp32.  low_hz / band_hz [C] in Hz; n_ [h] and window [h] are the module's tensors (:1904-1913).  packed (may be NULL):
+ *   the [ceil(C/8)][h][8] copy the convolutions read, pk_sincfast_work_floats(C, K) floats.
+ * pk_sincfast_fwd replaces the F.conv1d of :1951-1959 on that bank; the [C][K] bank is never built.
+ * pk_sincfast_bwd replaces autograd's conv1d backward and the backward of every operation of :1931-1947:  dlow / dband [C]
+ *   (the gradients of low_hz_ / band_hz_) from a reduction over the h left taps only, split over workgroups and added in a
+ *   fixed order (deterministic), and dx [B][n] if dx is not NULL.  half: what pk_sincfast_bank wrote for the same
+ *   parameters; partial: >= pk_sincfast_partial_floats(...) floats of scratch.
+ * Refused (2, with the numbers in pk_last_error): K even or < 3, s or d < 1, p < 0, C < 1, L_out < 1, and a geometry whose
+ *   window of a single output position, d*(K-1) + 1 words, does not fit 64 KB of LDS. */
+int64_t pk_sincfast_work_floats(int C, int K);
+int pk_sincfast_bank(void* stream, const float* low_hz, const float* band_hz, const float* n_, const float* window, int C, int K,
+                     float sample_rate, float min_low_hz, float min_band_hz, float* half, float* packed);
+int pk_sincfast_fwd(void* stream, const float* x, const float* packed, int B, int64_t n, int C, int K, int s, int p, int d, float* y);
+int64_t pk_sincfast_partial_floats(int B, int64_t n, int C, int K, int s, int p, int d);
+int pk_sincfast_bwd(void* stream, const float* x, const float* dy, const float* low_hz, const float* band_hz, const float* n_,
+                    const float* window, const float* half, int B, int64_t n, int C, int K, int s, int p, int d, float sample_rate,
+                    float min_low_hz, float min_band_hz, float* dlow, float* dband, float* dx, float* partial);
+
 /* persistent-recurrence health: number of spin time-outs since the last reset
  * (host-mapped counter, readable without a device sync). */
 unsigned pk_persist_error_count(void);

@@ -153,6 +153,12 @@ SIGNATURES = {
     "pk_logmel_fwd": (c_int, [P, P, P, P, c_int64, c_int, c_int, c_int, c_int, P]),
     "pk_chavg_fwd": (c_int, [P, P, P, c_int64, c_int, P]),
     "pk_chavg_bwd": (c_int, [P, P, P, c_int64, c_int, P]),
+    "pk_sincfast_work_floats": (c_int64, [c_int, c_int]),
+    "pk_sincfast_bank": (c_int, [P, P, P, P, P, c_int, c_int, c_float, c_float, c_float, P, P]),
+    "pk_sincfast_fwd": (c_int, [P, P, P, c_int, c_int64, c_int, c_int, c_int, c_int, c_int, P]),
+    "pk_sincfast_partial_floats": (c_int64, [c_int, c_int64, c_int, c_int, c_int, c_int, c_int]),
+    "pk_sincfast_bwd": (c_int, [P, P, P, P, P, P, P, P, c_int, c_int64, c_int, c_int, c_int, c_int, c_int, c_float, c_float,
+                                c_float, P, P, P, P]),
     "pk_persist_error_count": (ctypes.c_uint, []),
     "pk_persist_error_reset": (None, []),
     "pk_linear_bn_act_bf16_covers": (c_int, [c_int64, c_int64, c_int64]),

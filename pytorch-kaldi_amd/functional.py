@@ -2094,6 +2094,65 @@ def channel_average(x, w):
     return ChannelAverageFn.apply(x, w)
 
 
+# ----------------------------------------------------------------------------
+# SincConv_fast (csrc/pk_sincfast.hip): symmetric band-pass filters on one input channel, folded about the centre tap
+# ----------------------------------------------------------------------------
+class SincConvFastFn(torch.autograd.Function):
+    """neural_networks.py:1931-1959 as three launches forward (half bank, convolution) and three backward (bank again,
+    filter-gradient reduction + chain, data gradient if asked for).  Returns (y, half): half [C, (K-1)/2] is the left half
+    of the bank, not differentiable, for the module's lazy ``.filters``.  Saves x and the two parameters; backward
+    recomputes the half bank."""
+
+    @staticmethod
+    def forward(ctx, x, low_hz_, band_hz_, n_, window_, K, stride, padding, dilation, sample_rate, min_low_hz, min_band_hz):
+        _need_gpu(x, low_hz_, band_hz_, n_, window_)
+        K, s, p, d = int(K), int(stride), int(padding), int(dilation)
+        h, C = (K - 1) // 2, low_hz_.numel()
+        if x.dim() != 3 or x.shape[1] != 1 or band_hz_.numel() != C or n_.numel() != h or window_.numel() != h:
+            raise _lib.PkError("sinc_conv_fast: x [B, 1, n], low_hz_ / band_hz_ [C, 1], n_ / window_ of (K-1)/2 = %d values "
+                               "(got %s, %s, %s, %d, %d)" % (h, tuple(x.shape), tuple(low_hz_.shape), tuple(band_hz_.shape),
+                                                             n_.numel(), window_.numel()))
+        lib = _lib.load()
+        x = x.contiguous()
+        lo, ba = low_hz_.contiguous().view(-1), band_hz_.contiguous().view(-1)
+        n1, w1 = n_.contiguous().view(-1), window_.contiguous().view(-1)
+        B, n = x.shape[0], x.shape[2]
+        num = n + 2 * p - d * (K - 1) - 1
+        Lout = num // s + 1 if num >= 0 and s >= 1 else 0
+        half, packed = _new(C, h, like=x), _new(int(lib.pk_sincfast_work_floats(C, K)), like=x)
+        y = _new(B, C, Lout, like=x)
+        cfg = (B, n, C, K, s, p, d)
+        bank = (C, K, float(sample_rate), float(min_low_hz), float(min_band_hz))
+        _lib.check(lib.pk_sincfast_bank(_stream(), _p(lo), _p(ba), _p(n1), _p(w1), *bank, _p(half), _p(packed)), "pk_sincfast_bank")
+        _lib.check(lib.pk_sincfast_fwd(_stream(), _p(x), _p(packed), *cfg, _p(y)), "pk_sincfast_fwd")
+        ctx.save_for_backward(x, lo, ba, n1, w1)
+        ctx.cfg, ctx.bank, ctx.shapes = cfg, bank, (low_hz_.shape, band_hz_.shape)
+        ctx.mark_non_differentiable(half)
+        return y, half
+
+    @staticmethod
+    def backward(ctx, dy, _dhalf):
+        lib = _lib.load()
+        x, lo, ba, n1, w1 = ctx.saved_tensors
+        B, n, C, K, s, p, d = ctx.cfg
+        dy = dy.contiguous()
+        half = _new(C, (K - 1) // 2, like=x)
+        _lib.check(lib.pk_sincfast_bank(_stream(), _p(lo), _p(ba), _p(n1), _p(w1), *ctx.bank, _p(half), None), "pk_sincfast_bank")
+        part = _new(int(lib.pk_sincfast_partial_floats(*ctx.cfg)), like=x)
+        dlow, dband = _new(C, like=x), _new(C, like=x)
+        dx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
+        _lib.check(lib.pk_sincfast_bwd(_stream(), _p(x), _p(dy), _p(lo), _p(ba), _p(n1), _p(w1), _p(half), *ctx.cfg, *ctx.bank[2:],
+                                       _p(dlow), _p(dband), _p(dx), _p(part)), "pk_sincfast_bwd")
+        return (dx, dlow.view(ctx.shapes[0]), dband.view(ctx.shapes[1])) + (None,) * 9
+
+
+def sinc_conv_fast(x, low_hz_, band_hz_, n_, window_, K, stride, padding, dilation, sample_rate, min_low_hz, min_band_hz):
+    """x [B, 1, n] -> (y [B, C, L_out], half [C, (K-1)/2]): SincConv_fast's forward (K odd) with nn.Conv1d's stride /
+    padding / dilation.  Differentiable in x, low_hz_ and band_hz_."""
+    return SincConvFastFn.apply(x, low_hz_, band_hz_, n_, window_, K, stride, padding, dilation, sample_rate, min_low_hz,
+                                min_band_hz)
+
+
 class LnLastActDropFn(torch.autograd.Function):
     """drop(act(LayerNorm(z))) behind a conv layer's max-pool as ONE launch each way (pk_ln_last_act_drop_*), the CNN /
     SincNet flavour of the reference's LayerNorm (features [C, L], statistics over the last dim:

@@ -41,6 +41,10 @@ shapes and initial distributions are the reference's, the initial values are not
 over the microphones, then framing, Hann window, DFT, power, mel filterbank and log10 as one launch (pk_logmel.hip).  The
 filterbank is built from torchaudio's formula, not on the package; parity with a torchaudio install is unverified.
 
+``SincConv_fast`` (neural_networks.py:1816-1959) is the sinc layer of the released SincNet code with nn.Conv1d's stride,
+padding and dilation, for a user's own arch file: ``SincConv_fast(1, C, K, ...)(waveforms [B, 1, n])``; bank synthesis,
+convolution and all gradients are HIP kernels that fold each symmetric filter about its centre tap (pk_sincfast.hip).
+
 The nn.Linear / nn.BatchNorm1d / nn.Conv1d sub-modules are parameter containers
 only: ``forward`` never calls them, it hands their tensors to the HIP kernels
 through ``functional``.  There is no CPU path: ``use_cuda`` must be True.
@@ -1553,6 +1557,60 @@ class SincConv(nn.Module):
         mx, _ = torch.max(bp, dim=1, keepdim=True)
         bp = bp / mx
         return (bp * self.window_).view(self.out_channels, 1, self.kernel_size)
+
+
+class SincConv_fast(nn.Module):
+    """neural_networks.py:1816-1959: constructor signature, defaults, ValueErrors, parameters (low_hz_, band_hz_ [C, 1] in Hz,
+    mel-spaced) and the plain tensor attributes n_ / window_ (the left half of the time axis and of the Hamming window, with
+    the reference's linspace(0, K/2 - 1, int(K/2)) abscissae) are the reference's.  forward(waveforms [B, 1, n]) ->
+    [B, C, L_out] runs functional.sinc_conv_fast: the filters are symmetric about a centre tap of 1, so only their left half
+    is ever synthesised, multiplied or differentiated.  ``.filters`` [C, 1, K] exists after a forward, as in the reference,
+    assembled from that half when read (detached)."""
+
+    to_mel = staticmethod(SincConv.to_mel)
+    to_hz = staticmethod(SincConv.to_hz)
+
+    def __init__(self, in_channels, out_channels, kernel_size, stride=1, padding=0, dilation=1, bias=False, groups=1,
+                 sample_rate=16000, min_low_hz=50, min_band_hz=50):
+        super().__init__()
+        if in_channels != 1:
+            raise ValueError("SincConv only support one input channel (here, in_channels = {%i})" % (in_channels))
+        self.out_channels = out_channels
+        self.kernel_size = kernel_size + 1 if kernel_size % 2 == 0 else kernel_size
+        self.stride, self.padding, self.dilation = stride, padding, dilation
+        if bias:
+            raise ValueError("SincConv does not support bias.")
+        if groups > 1:
+            raise ValueError("SincConv does not support groups.")
+        self.sample_rate, self.min_low_hz, self.min_band_hz = sample_rate, min_low_hz, min_band_hz
+        low_hz = 30
+        high_hz = self.sample_rate / 2 - (self.min_low_hz + self.min_band_hz)
+        mel = np.linspace(self.to_mel(low_hz), self.to_mel(high_hz), self.out_channels + 1)
+        hz = self.to_hz(mel)
+        self.low_hz_ = nn.Parameter(torch.Tensor(hz[:-1]).view(-1, 1))
+        self.band_hz_ = nn.Parameter(torch.Tensor(np.diff(hz)).view(-1, 1))
+        n_lin = torch.linspace(0, (self.kernel_size / 2) - 1, steps=int((self.kernel_size / 2)))
+        self.window_ = 0.54 - 0.46 * torch.cos(2 * math.pi * n_lin / self.kernel_size)
+        n = (self.kernel_size - 1) / 2.0
+        self.n_ = 2 * math.pi * torch.arange(-n, 0).view(1, -1) / self.sample_rate
+        self._half = None
+
+    @property
+    def filters(self):
+        if self._half is None:
+            raise AttributeError("SincConv_fast.filters exists after the first forward")
+        centre = torch.ones(self.out_channels, 1, device=self._half.device)
+        return torch.cat([self._half, centre, torch.flip(self._half, dims=[1])], dim=1).view(self.out_channels, 1, self.kernel_size)
+
+    def forward(self, waveforms):
+        if not waveforms.is_cuda:
+            raise PkError("pytorch-kaldi_amd.nn.SincConv_fast runs on the GPU only: move the module and its input there")
+        self.n_ = self.n_.to(waveforms.device)
+        self.window_ = self.window_.to(waveforms.device)
+        y, self._half = F_.sinc_conv_fast(waveforms, self.low_hz_, self.band_hz_, self.n_, self.window_, self.kernel_size,
+                                          self.stride, self.padding, self.dilation, self.sample_rate, self.min_low_hz,
+                                          self.min_band_hz)
+        return y
 
 
 class _ConvStack(nn.Module):
