@@ -492,6 +492,28 @@ int pk_fused_step_ex(void* stream, int kind, float* p, float* g, float* s0, floa
 int pk_quat_assemble(void* stream, const float* const* comps, const float* base, int G, int I, int O, float* W);
 int pk_quat_fold(void* stream, const float* dW, int G, int I, int O, float beta, float* const* dcomps, float* dbase);
 
+/* ---- quaternion linear layer without its real matrix (pk_quat_linear.hip; quaternion_linear, quaternion_neural_networks.py:
+ * 378-405, and QuaternionLinearFunction, :408-477).  Components comp[c] [I][O] and the sign table S as above; activations
+ * X [N][4*I], Y / dY [N][4*O], dense and row-major, the four blocks side by side:
+ *     pk_quat_linear_fwd     Y[n][q*O + o]  = bias[q*O + o] + sum_p S[q][p] * sum_i X[n][p*I + i] * comp[q ^ p][i][o]   (:388-405)
+ *     pk_quat_linear_bwd_x   dX[n][p*I + i] = sum_q S[q][p] * sum_o dY[n][q*O + o] * comp[q ^ p][i][o]                 (:438-442, :465)
+ *     pk_quat_linear_bwd_w   dcomp[c][i][o] = beta * dcomp[c][i][o] + sum_q S[q][q ^ c] * sum_n X[n][(q ^ c)*I + i] * dY[n][q*O + o]
+ *                            dbias[q*O + o] = sum_n dY[n][q*O + o]   when dbias is not NULL                            (:444-475)
+ * One launch each for the first two, two for the third (the rows are split over workgroups, the partial sums go through
+ * `workspace`, pk_quat_linear_work_floats(N, I, O) floats, and are added in a fixed order: bit-identical from run to run).
+ * The real [4*O][4*I] matrix, its gradient and the fold do not exist.  prec: PK_PREC_F32 (exact) or PK_PREC_BF16 (operands
+ * rounded to bf16 while staging, fp32 accumulation; dbias adds the unrounded dY).  bias may be NULL.  beta is 0 (overwrite,
+ * the old contents are not read) or 1.  The four components are named by `comps` / `dcomps` (a HOST array of four device
+ * pointers) or by `base` / `dbase` (back to back), the other being NULL, as for pk_quat_assemble.  N, I, O >= 1 of any
+ * parity; I, O <= 2^20, I * O <= 2^30, N < 2^31, N * 4 * max(I, O) <= 2^40 (pk_quat_linear_work_floats gives 0 outside). */
+int64_t pk_quat_linear_work_floats(int64_t N, int I, int O);
+int pk_quat_linear_fwd(void* stream, int prec, int64_t N, int I, int O, const float* X, const float* const* comps,
+                       const float* base, const float* bias, float* Y);
+int pk_quat_linear_bwd_x(void* stream, int prec, int64_t N, int I, int O, const float* dY, const float* const* comps,
+                         const float* base, float* dX);
+int pk_quat_linear_bwd_w(void* stream, int prec, int64_t N, int I, int O, const float* X, const float* dY, float beta,
+                         float* const* dcomps, float* dbase, float* dbias, float* workspace);
+
 /* ---- torch-layout recurrent layers on the engine's cells (pk_pack.hip; the cuDNN wrappers, neural_networks.py:153-203 and
  * :256-297).  torch.nn.LSTM / nn.RNN keep, per layer and direction, weight_ih [G*H][D], weight_hh [G*H][H] and two biases
  * [G*H] with the gate blocks in torch's order (LSTM: i, f, g, o); the recurrence entries take Wcat / Ucat / one bias in the

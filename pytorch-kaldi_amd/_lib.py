@@ -137,6 +137,10 @@ SIGNATURES = {
                                  c_int, P, c_int, P]),
     "pk_quat_assemble": (c_int, [P, P, P, c_int, c_int, c_int, P]),
     "pk_quat_fold": (c_int, [P, P, c_int, c_int, c_int, c_float, P, P]),
+    "pk_quat_linear_work_floats": (c_int64, [c_int64, c_int, c_int]),
+    "pk_quat_linear_fwd": (c_int, [P, c_int, c_int64, c_int, c_int, P, P, P, P, P]),
+    "pk_quat_linear_bwd_x": (c_int, [P, c_int, c_int64, c_int, c_int, P, P, P, P]),
+    "pk_quat_linear_bwd_w": (c_int, [P, c_int, c_int64, c_int, c_int, P, P, c_float, P, P, P, P]),
     "pk_gates_pack": (c_int, [P, P, P, P, P, c_int, c_int, c_int, P, P, P, P]),
     "pk_gates_unpack": (c_int, [P, P, P, P, c_int, c_int, c_int, P, P, P, P, P]),
     "pk_seq_join_fwd": (c_int, [P, P, P, P, c_float, c_int64, c_int64, c_int64, c_int, P, P]),

@@ -1541,6 +1541,76 @@ def quat_matrix(comps, G, I, O):
     return QuatMatrixFn.apply(*comps, G, I, O)
 
 
+def _quat_names(comps):
+    """(keep-alive, table, base) of four components for the pk_quat_linear_* entries: one base pointer when they lie
+    back to back (adjacent_view), else a host table of their addresses."""
+    whole = adjacent_view(comps)
+    if whole is not None:
+        return whole, None, _p(whole)
+    arr, table = _quat_table(comps)
+    return arr, table, None
+
+
+class QuatLinearFn(torch.autograd.Function):
+    """y = quaternion_linear(x, r, i, j, k, bias) (quaternion_neural_networks.py:378-405; its hand-written backward
+    :408-477) on the fused Hamilton-product kernels of pk_quat_linear.hip: one launch forward, one for dX, two for the
+    four component gradients and dbias.  The real [4*O, 4*I] matrix is never built.  x is [N, 4*I] or [T, B, 4*I];
+    saved for backward: x and the four components."""
+
+    @staticmethod
+    def forward(ctx, x, r, i, j, k, bias):
+        comps = (r, i, j, k)
+        if x.dim() not in (2, 3):
+            raise _lib.PkError("quat_linear: the input is [N, 4*I] or [T, B, 4*I] (got %s)" % (tuple(x.shape),))
+        I, O = (int(d) for d in r.shape) if r.dim() == 2 else (0, 0)
+        if I < 1 or O < 1 or any(tuple(c.shape) != (I, O) for c in comps):
+            raise _lib.PkError("quat_linear: four components of one shape [I, O] (got %s)" % [tuple(c.shape) for c in comps])
+        if x.shape[-1] != 4 * I or x.numel() == 0:
+            raise _lib.PkError("quat_linear: components [%d, %d] take a non-empty input whose last dimension is 4 * %d = %d "
+                               "(got %s)" % (I, O, I, 4 * I, tuple(x.shape)))
+        if bias is not None and tuple(bias.shape) != (4 * O,):
+            raise _lib.PkError("quat_linear: the bias of components [%d, %d] is [%d] (got %s)" % (I, O, 4 * O, tuple(bias.shape)))
+        _need_gpu(x, *comps, bias)
+        x2 = x.detach().reshape(-1, 4 * I).contiguous()
+        comps = [c.detach().contiguous() for c in comps]
+        N = x2.shape[0]
+        y = _new(N, 4 * O, like=x2)
+        keep, table, base = _quat_names(comps)
+        b = None if bias is None else bias.detach().contiguous()
+        _lib.check(_lib.load().pk_quat_linear_fwd(_stream(), entry_prec(), N, I, O, _p(x2), table, base, _p(b), _p(y)),
+                   "pk_quat_linear_fwd")
+        ctx.save_for_backward(x2, *comps)
+        ctx.dims, ctx.in_shape, ctx.prec = (N, I, O), x.shape, entry_prec()
+        return y.view(*x.shape[:-1], 4 * O)
+
+    @staticmethod
+    def backward(ctx, dy):
+        x2, *comps = ctx.saved_tensors
+        N, I, O = ctx.dims
+        lib = _lib.load()
+        dy2 = dy.reshape(N, 4 * O).contiguous()
+        dx = db = None
+        dc = [None] * 4
+        if ctx.needs_input_grad[0]:
+            dx = _new(N, 4 * I, like=dy2)
+            keep, table, base = _quat_names(comps)
+            _lib.check(lib.pk_quat_linear_bwd_x(_stream(), ctx.prec, N, I, O, _p(dy2), table, base, _p(dx)), "pk_quat_linear_bwd_x")
+            dx = dx.view(ctx.in_shape)
+        want_b = ctx.needs_input_grad[5]
+        if any(ctx.needs_input_grad[1:5]) or want_b:
+            d = _new(4, I, O, like=dy2)
+            db = _new(4 * O, like=dy2) if want_b else None
+            ws = _new(int(lib.pk_quat_linear_work_floats(N, I, O)), like=dy2)
+            _lib.check(lib.pk_quat_linear_bwd_w(_stream(), ctx.prec, N, I, O, _p(x2), _p(dy2), 0.0, None, _p(d), _p(db), _p(ws)),
+                       "pk_quat_linear_bwd_w")
+            dc = [d[c] if ctx.needs_input_grad[1 + c] else None for c in range(4)]
+        return (dx, *dc, db)
+
+
+def quat_linear(x, r, i, j, k, bias=None):
+    return QuatLinearFn.apply(x, r, i, j, k, bias)
+
+
 # ----------------------------------------------------------------------------
 # torch-layout recurrent layers (the cuDNN wrappers, neural_networks.py:153-203, :256-297)
 # ----------------------------------------------------------------------------

@@ -751,28 +751,100 @@ class _QuatLinear(nn.Module):
 
     def __init__(self, in_features, out_features, bias=True):
         super().__init__()
-        self.in_features, self.out_features = in_features // 4, out_features // 4
-        shape = (self.in_features, self.out_features)
-        self.seed = np.random.randint(0, 1234)
-        rng = np.random.RandomState(np.random.randint(1, 1234))
-        s = 1.0 / np.sqrt(2 * (shape[0] + shape[1]))
-        modulus = _chi4(s, shape)
-        n = shape[0] * shape[1]
-        v_i, v_j, v_k = (np.random.normal(0, 1.0, n) for _ in range(3))
-        norm = np.sqrt(v_i ** 2 + v_j ** 2 + v_k ** 2 + 0.0001)  # (the reference's element loop, all elements at once)
-        v_i, v_j, v_k = ((v / norm).reshape(shape) for v in (v_i, v_j, v_k))
-        phase = rng.uniform(low=-np.pi, high=np.pi, size=shape)
-        comps = (modulus * np.cos(phase), modulus * v_i * np.sin(phase), modulus * v_j * np.sin(phase),
-                 modulus * v_k * np.sin(phase))
-        for name, w in zip(("r_weight", "i_weight", "j_weight", "k_weight"), comps):
-            setattr(self, name, nn.Parameter(torch.from_numpy(w).float()))
-        if bias:
-            self.bias = nn.Parameter(torch.zeros(self.out_features * 4))
-        else:
-            self.register_parameter("bias", None)
+        _quat_setup(self, in_features, out_features, bias, "glorot", "quaternion", None, bias_parameter_only=True)
 
     def components(self):
         return [self.r_weight, self.i_weight, self.j_weight, self.k_weight]
+
+
+QUAT_INITS = ("quaternion", "unitary", "random")
+
+
+def _quat_init(shape, weight_init, criterion):
+    """The four component arrays (float64) of quaternion_init / unitary_init / random_init (quaternion_neural_networks.py:
+    574-626, :483-529, :531-571), drawn from numpy's GLOBAL generator in the reference's order; the reference's element
+    loops are done on whole arrays, operation by operation."""
+    if criterion == "glorot":
+        s = 1.0 / np.sqrt(2 * (shape[0] + shape[1]))
+    elif criterion == "he":
+        s = 1.0 / np.sqrt(2 * shape[0])
+    else:
+        raise ValueError("Invalid criterion: " + str(criterion))
+    n = shape[0] * shape[1]
+    if weight_init == "quaternion":
+        rng = np.random.RandomState(np.random.randint(1, 1234))  # the phase generator (:591)
+        modulus = _chi4(s, shape)
+        v_i, v_j, v_k = (np.random.normal(0, 1.0, n) for _ in range(3))
+        norm = np.sqrt(v_i ** 2 + v_j ** 2 + v_k ** 2 + 0.0001)
+        v_i, v_j, v_k = ((v / norm).reshape(shape) for v in (v_i, v_j, v_k))
+        phase = rng.uniform(low=-np.pi, high=np.pi, size=shape)
+        return (modulus * np.cos(phase), modulus * v_i * np.sin(phase), modulus * v_j * np.sin(phase),
+                modulus * v_k * np.sin(phase))
+    if weight_init == "unitary":
+        s = np.sqrt(3.0) * s
+        v = [np.random.uniform(-s, s, n) for _ in range(4)]
+        norm = np.sqrt(v[0] ** 2 + v[1] ** 2 + v[2] ** 2 + v[3] ** 2) + 0.0001
+        return tuple((c / norm).reshape(shape) for c in v)
+    if weight_init == "random":
+        v = [np.random.uniform(0.0, 1.0, n) for _ in range(4)]
+        return tuple(c.reshape(shape) * s for c in v)
+    raise ValueError("Invalid weight_init: " + str(weight_init))
+
+
+def _quat_setup(mod, in_features, out_features, bias, init_criterion, weight_init, seed, bias_parameter_only):
+    """What the constructors of the reference's quaternion linear classes do (:180-209, :228-257), in their order: the
+    layer's seed from numpy's global generator when none is given, the layer's RandomState (handed to the initialiser,
+    which draws nothing from it), the four components, a zero bias.  bias_parameter_only: without bias the name is
+    registered as None (:243); else it is a plain zero vector that is no parameter (:196)."""
+    mod.in_features, mod.out_features = in_features // 4, out_features // 4
+    mod.init_criterion, mod.weight_init = init_criterion, weight_init
+    mod.seed = seed if seed is not None else np.random.randint(0, 1234)
+    mod.rng = np.random.RandomState(mod.seed)
+    comps = _quat_init((mod.in_features, mod.out_features), weight_init, init_criterion)
+    for name, w in zip(("r_weight", "i_weight", "j_weight", "k_weight"), comps):
+        setattr(mod, name, nn.Parameter(torch.from_numpy(w).float()))
+    if bias:
+        mod.bias = nn.Parameter(torch.zeros(mod.out_features * 4))
+    elif bias_parameter_only:
+        mod.register_parameter("bias", None)
+    else:
+        mod.bias = torch.zeros(mod.out_features * 4)
+
+
+class QuaternionLinearAutograd(nn.Module):
+    """quaternion_neural_networks.py:175-221: y = x (*) W + b with W the Hamilton-product matrix of the four components
+    [in / 4, out / 4], on the fused kernels of functional.quat_linear (the real matrix is never built).  Initialisers
+    'quaternion', 'unitary' and 'random', criteria 'glorot' and 'he'; np.random.seed gives the reference's weights.
+    Without bias the reference keeps a zero vector that is no parameter and adds it; here it is kept and not added."""
+    INITS, BIAS_NONE_WHEN_OFF = QUAT_INITS, False
+
+    def __init__(self, in_features, out_features, bias=True, init_criterion="glorot", weight_init="quaternion", seed=None):
+        super().__init__()
+        if weight_init not in self.INITS:
+            raise ValueError("%s: weight_init %r (one of %s)" % (type(self).__name__, weight_init, ", ".join(self.INITS)))
+        _quat_setup(self, in_features, out_features, bias, init_criterion, weight_init, seed,
+                    bias_parameter_only=self.BIAS_NONE_WHEN_OFF)
+
+    def forward(self, input):
+        bias = self.bias if isinstance(self.bias, nn.Parameter) else None
+        return F_.quat_linear(input, self.r_weight, self.i_weight, self.j_weight, self.k_weight, bias)
+
+    def __repr__(self):
+        return (self.__class__.__name__ + "(" + "in_features=" + str(self.in_features) + ", out_features=" + str(self.out_features)
+                + ", bias=" + str(self.bias is not None) + ", init_criterion=" + str(self.init_criterion)
+                + ", weight_init=" + str(self.weight_init) + ", seed=" + str(self.seed) + ")")
+
+
+class QuaternionLinear(QuaternionLinearAutograd):
+    """quaternion_neural_networks.py:223-280: the form with the hand-written backward.  The same engine function as
+    QuaternionLinearAutograd - the two are one function in the reference too - with the reference's differences:
+    'quaternion' and 'unitary' only, `bias` registered as None when off, inputs of 2 or 3 dimensions only."""
+    INITS, BIAS_NONE_WHEN_OFF = QUAT_INITS[:2], True
+
+    def forward(self, input):
+        if input.dim() not in (2, 3):
+            raise NotImplementedError
+        return super().forward(input)
 
 
 class QLSTM(_Recurrent):
