@@ -1,10 +1,13 @@
 """nn.fusionRNN_jit without a GPU: state-dict names, order and shapes, out_dim and the width chain, the refusals at
 construction, tanh for an unknown activation string, layer 0 fusing whatever fusionRNN_do_fusion says, the flat-parameter
-layout and the refusal of a CPU tensor."""
+layout and the refusal of a CPU tensor; and what test_gpu_fusion.py's dispatch-path cases assume of their inputs (the path
+arithmetic, the distance from the kink or the zeroed cotangent) and of the entries' refusals."""
 import importlib
 
 import pytest
 import torch
+
+import fusion_cases as fc
 
 nn_amd = importlib.import_module("pytorch-kaldi_amd.nn")
 _lib = importlib.import_module("pytorch-kaldi_amd._lib")
@@ -65,3 +68,55 @@ def test_unknown_activation_is_tanh_and_layer_0_always_fuses():
 def test_cpu_tensor_is_refused():
     with pytest.raises(_lib.PkError):
         nn_amd.fusionRNN_jit(_opts(), 12)(torch.randn(5, 2, 12))
+
+
+# ---- the input conditions of test_gpu_fusion.py's dispatch-path cases, so that a failure on the GPU can only mean the kernel
+
+@pytest.mark.parametrize("shape", list(fc.PATHS))
+def test_path_shapes_reach_the_paths_their_comments_name(shape):
+    g = fc.geometry(shape)
+    assert g == fc.EXPECT[shape]
+    assert shape[2] <= fc.MAX_F and g["nks"] <= g["NKS"] and g["width"] <= fc.MAX_WIDTH[True]
+    parts = fc.ws_parts(_lib.load(), shape)  # the library's own arithmetic (pk_fusion_ws_floats runs on the host)
+    assert parts == 4 * g["walkers"]
+    if shape in fc.WALKS:
+        # a ragged walk: more row tiles than walkers, and no multiple of them
+        assert g["walkers"] < g["rtiles"] and g["rtiles"] % g["walkers"] and g["last_rows"] < 64
+    else:
+        assert g["walkers"] == g["rtiles"]
+
+
+def test_path_shapes_cover_what_the_older_shapes_leave():
+    reached ={fc.geometry(s)["NKS"]: fc.geometry(s)["nks"] for s in fc.SHAPES}
+    assert reached == {1: 1, 4: 3}  # what the older shapes reach: the instances and step counts left to the new ones
+    assert {(fc.geometry(s)["NKS"], fc.geometry(s)["nks"]) for s in fc.PATHS} >= {(2, 2), (4, 4), (8, 8), (8, 5)}
+    assert all(any(fc.geometry(s)["width"] == fc.MAX_WIDTH[bf] for s in fc.PATHS) for bf in (False, True))
+
+
+@pytest.mark.parametrize("shape,act,reduce,bf", fc.path_cases())
+def test_path_cases_keep_off_the_kink(shape, act, reduce, bf):
+    case = fc.proj_case(shape, act, reduce, bf)
+    x, W, b, slope, cot = case.inputs
+    print(shape, act, reduce, "bf16" if bf else "fp32", "min |pre| %.2e, zeroed share %.2e" % (case.kink, case.zeroed))
+    assert all(bool(torch.isfinite(t).all()) for t in case.ref.values())
+    if shape in fc.WALKS and act != "tanh":
+        near = (fc.run_pre(x, W, b, slope, shape[1], act, reduce, bf).abs() < fc.KINK).any(1)
+        assert 0 < case.zeroed <= fc.ZEROED_MAX and not cot[near].any() and bool((cot[~near] != 0).all())
+    else:
+        assert case.zeroed == 0.0 and bool((cot != 0).all())
+        assert act == "tanh" or case.kink >= fc.KINK, case.kink
+
+
+@pytest.mark.parametrize("shape,bf,words", fc.REFUSED)
+def test_geometry_is_refused_before_anything_else_is_looked_at(shape, bf, words):
+    """Both entries check the geometry first: with every pointer NULL a refused shape gives its own message, and a shape at
+    the limit gets as far as the pointer check.  Neither launches anything."""
+    lib = _lib.load()
+    fwd = lambda s: lib.pk_fusion_fwd(None, int(bf), *s, 1, 0, None, None, None, None, None)  # noqa: E731
+    bwd = lambda s: lib.pk_fusion_bwd(None, int(bf), *s, 1, 0, *[None] * 10)  # noqa: E731
+    N, M, F, H0 = shape
+    at_limit = (N, M, fc.MAX_F, H0) if F > fc.MAX_F else (N, fc.MAX_WIDTH[bf] // (16 * fc.geometry(shape)["nks"]), F, H0)
+    assert fc.geometry(at_limit)["width"] == fc.MAX_WIDTH[bf] or at_limit[2] == fc.MAX_F
+    for call in (fwd, bwd):
+        assert call(shape) == 2 and words in lib.pk_last_error().decode()
+        assert call(at_limit) == 2 and "NULL" in lib.pk_last_error().decode()

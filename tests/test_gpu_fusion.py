@@ -2,24 +2,24 @@
 fp32 mode: norm-relative error below 1e-4.  bf16 mode: against the same reference with its GEMM operands rounded to bf16,
 err < max(1e-4, 2 * d0), d0 = that reference's distance from itself when x moves by a relative 2^-24 in front of the rounding
 (the rule of test_gpu_sru.py).  Seeds are chosen so that no piecewise-linear pre-activation of the reference lies within 1e-5
-of its kink.  Each test prints what it measured."""
+of its kink; on the two shapes of thousands of rows, where no seed can, the cotangent is zero at those entries instead
+(fusion_cases.py builds every case and test_fusion_host.py checks these conditions on the CPU).  Each test prints what it
+measured."""
 import functools
 import importlib
 
 import pytest
 import torch
 
-from fusion_ref import fusion_proj_ref, fusion_rnn_ref
+from fusion_cases import KINK, REFUSED, SHAPES, WALKS, ZEROED_MAX, geometry, path_cases, proj_case, ws_parts
+from fusion_ref import fusion_rnn_ref
 from golden_util import rel_err
 
 pytestmark = pytest.mark.gpu
 F_ = importlib.import_module("pytorch-kaldi_amd.functional")
 nn_amd = importlib.import_module("pytorch-kaldi_amd.nn")
-TOL, KINK = 1e-4, 1e-5
-
-# (N, M, F, H0) -> seed.  Tiles are 64 rows x 64 columns of the 2*H0 stacked ones, K steps of 16: below one tile both ways;
-# rows and columns across tiles with a remainder, F below one K step, M = 1; F = 40 (three K steps in the four-step kernel).
-SHAPES = {(21, 6, 13, 20): 0, (150, 1, 5, 72): 0, (130, 2, 40, 136): 0}
+_lib = importlib.import_module("pytorch-kaldi_amd._lib")
+TOL = 1e-4
 
 
 def graded(got, ref, d0):
@@ -29,46 +29,18 @@ def graded(got, ref, d0):
         assert e < (max(TOL, 2 * d0[n]) if d0 else TOL), (n, e, d0 and d0[n])
 
 
-@functools.lru_cache(maxsize=None)
-def proj_case(shape, act, reduce, bf):
-    """Inputs, the reference's results and d0 (bf16 only) of one projection case; the reference runs once per case."""
-    N, M, F, H0 = shape
-    g = torch.Generator().manual_seed(SHAPES[shape])
-    x, W = torch.randn(N, M * F, generator=g), torch.randn(2 * H0, F, generator=g) / F ** 0.5
-    b, slope = 0.3 * torch.randn(2 * H0, generator=g), torch.tensor([0.25, 0.1]) if act == "prelu" else None
-    cot = torch.randn(N, 2 * H0, generator=g)
-    eps = torch.randint(0, 2, x.shape, generator=g).double() * 2 - 1
-
-    def run(xin):
-        leaves = [None if t is None else t.double().requires_grad_() for t in (xin, W, b, slope)]
-        pres = []
-        P = fusion_proj_ref(*leaves, M, act, reduce, bf, pres)
-        (P * cot.double()).sum().backward()
-        out = {"P": P.detach(), "dx": leaves[0].grad, "dW": leaves[1].grad, "db": leaves[2].grad}
-        if slope is not None:
-            out["dslope"] = leaves[3].grad
-        return out, float(pres[0].abs().min())
-
-    ref, kink = run(x)
-    d0 = None
-    if bf:
-        pert = run(x.double() * (1 + 2.0 ** -24 * eps))[0]
-        d0 = {n: rel_err(pert[n], ref[n]) for n in ref}
-    return (x, W, b, slope, cot), ref, d0, kink
-
-
-def run_proj(inputs, M, act, reduce, bf):
+def run_proj(inputs, M, act, reduce, bf, need_dx=True):
     x, W, b, slope, cot = (None if t is None else t.cuda() for t in inputs)
-    leaves = [None if t is None else t.requires_grad_() for t in (x, W, b, slope)]
+    leaves = [None if t is None else t.requires_grad_() for t in (W, b, slope)]
     F_.set_precision("bf16" if bf else "fp32")
     try:
-        P = F_.fusion_proj(*leaves, M, act, reduce)
+        P = F_.fusion_proj(x.requires_grad_(need_dx), *leaves, M, act, reduce)
         (P * cot).sum().backward()
     finally:
         F_.set_precision("fp32")
-    out = {"P": P, "dx": leaves[0].grad, "dW": leaves[1].grad, "db": leaves[2].grad}
+    out = {"P": P.detach(), "dx": x.grad, "dW": leaves[0].grad, "db": leaves[1].grad}
     if slope is not None:
-        out["dslope"] = leaves[3].grad
+        out["dslope"] = leaves[2].grad
     return out
 
 
@@ -77,10 +49,27 @@ def run_proj(inputs, M, act, reduce, bf):
 @pytest.mark.parametrize("act", ["relu", "leaky_relu", "prelu", "tanh"])
 @pytest.mark.parametrize("shape", list(SHAPES))
 def test_projection_matches_reference(shape, act, reduce, bf):
-    inputs, ref, d0, kink = proj_case(shape, act, reduce, bf)
+    case = proj_case(shape, act, reduce, bf)
     if act != "tanh":
-        assert kink >= KINK, kink
-    graded(run_proj(inputs, shape[1], act, reduce, bf), ref, d0)
+        assert case.kink >= KINK, case.kink
+    graded(run_proj(case.inputs, shape[1], act, reduce, bf), case.ref, case.d0)
+
+
+@pytest.mark.parametrize("shape,act,reduce,bf", path_cases(),
+                         ids=["%s-%s-%s-%s" % ("x".join(map(str, s)), a, r, "bf16" if bf else "fp32") for s, a, r, bf in path_cases()])
+def test_projection_paths_match_reference(shape, act, reduce, bf):
+    """One shape per path of the dispatch (fusion_cases.PATHS says which), by the bounds of the test above."""
+    case = proj_case(shape, act, reduce, bf)
+    if shape in WALKS:
+        # the library's own workspace says that a workgroup of the weight-gradient kernel walks more than one row tile
+        parts, rtiles = ws_parts(_lib.load(), shape), geometry(shape)["rtiles"]
+        print("%d wave partials = %d walkers for %d row tiles; cotangent zeroed at a share of %.2e" % (parts, parts // 4, rtiles,
+                                                                                                    case.zeroed))
+        assert parts % 4 == 0 and parts // 4 < rtiles == -(-shape[0] // 64)
+        assert case.zeroed <= ZEROED_MAX, case.zeroed  # a condition on the inputs
+    elif act != "tanh":
+        assert case.kink >= KINK, case.kink
+    graded(run_proj(case.inputs, shape[1], act, reduce, bf), case.ref, case.d0)
 
 
 def test_projection_backward_is_deterministic():
@@ -88,6 +77,36 @@ def test_projection_backward_is_deterministic():
     inputs = proj_case(shape, "prelu", "sum", False)[0]
     a, b = run_proj(inputs, shape[1], "prelu", "sum", False), run_proj(inputs, shape[1], "prelu", "sum", False)
     assert all(torch.equal(a[n], b[n]) for n in a)
+
+
+def test_walked_backward_is_deterministic():
+    shape = (8229, 2, 24, 20)  # three, or two, row tiles per workgroup: the partials are still added in a fixed order
+    inputs = proj_case(shape, "prelu", "sum", False).inputs
+    a, b = run_proj(inputs, shape[1], "prelu", "sum", False), run_proj(inputs, shape[1], "prelu", "sum", False)
+    assert all(torch.equal(a[n], b[n]) for n in a)
+
+
+@pytest.mark.parametrize("bf", [False, True], ids=["fp32", "bf16"])
+@pytest.mark.parametrize("shape", [(8229, 2, 24, 20), (150, 1, 5, 72)])
+def test_backward_without_the_input_gradient(shape, bf):
+    """What nn.fusionRNN_jit runs: x is the network input and needs no gradient, so pk_fusion_bwd gets dx = NULL and skips
+    the dx kernel.  Everything else must keep its bits."""
+    inputs = proj_case(shape, "prelu", "sum", bf).inputs
+    full, lean = run_proj(inputs, shape[1], "prelu", "sum", bf), run_proj(inputs, shape[1], "prelu", "sum", bf, need_dx=False)
+    assert full["dx"] is not None and lean.pop("dx") is None
+    assert sorted(lean) == ["P", "dW", "db", "dslope"] and all(torch.equal(lean[n], full[n]) for n in lean)
+
+
+@pytest.mark.parametrize("shape,bf,words", REFUSED)
+def test_refusals_one_step_beyond_the_limits(shape, bf, words):
+    N, M, F, H0 = shape
+    F_.set_precision("bf16" if bf else "fp32")
+    try:
+        with pytest.raises(_lib.PkError, match=words):
+            F_.fusion_proj(torch.zeros(N, M * F).cuda(), torch.zeros(2 * H0, F).cuda(), torch.zeros(2 * H0).cuda(), None, M, "relu",
+                           "sum")
+    finally:
+        F_.set_precision("fp32")
 
 
 T, B, M, F, P_DROP = 9, 3, 3, 4, 0.2

@@ -1,60 +1,104 @@
 """SRU on the GPU: functional.sru_scan and nn.SRU against the float64 reference of sru_ref.py (norm-relative errors, the
 project's fp32 bound 1e-4), the bf16 mode against the same reference with its GEMM operands rounded to bf16, and padded
-batches under functional.sentence_lengths against every sentence alone.  Each test prints what it measured."""
+batches under functional.sentence_lengths against every sentence alone.  sru_cases.py builds the scan cases and says which
+path of the kernels each one enters; test_sru_host.py checks their input conditions on the CPU.  Each test prints what it
+measured."""
+import ctypes
 import importlib
 
 import pytest
 import torch
 
 from golden_util import rel_err
+from sru_cases import (CLAMP_CASE, CLAMP_LENS, LENS, LENS_CASES, MIN_C, RING, SCAN, ScanCase, leaves, scan_inputs, scan_loss,
+                       scan_reference)
 from sru_ref import sru_layer_ref, sru_scan_ref
 
 pytestmark = pytest.mark.gpu
 F_ = importlib.import_module("pytorch-kaldi_amd.functional")
 nn_amd = importlib.import_module("pytorch-kaldi_amd.nn")
+_lib = importlib.import_module("pytorch-kaldi_amd._lib")
 TOL = 1e-4
 
-# (T, B, D, H, k, act, mask_h, seed): T below, across and no multiple of the prefetch depth; 120 columns (one wave over the
-# direction and the sentence boundary); odd H at the 12-byte pitch; an exact multiple of the wave.  k = 3 comes with a skip
-# source except in the one-column case.  Seeds of the relu / selu cases: the reference has min |c_t| >= 1e-3.
-SCAN = [(1, 1, 1, 1, 3, "none", False, 0), (3, 2, 2, 5, 4, "tanh", False, 1), (37, 3, 2, 20, 3, "relu", True, 122),
-        (70, 2, 1, 67, 4, "selu", True, 11774), (130, 5, 2, 64, 3, "none", False, 4)]
 
-
-def scan_inputs(T, B, D, H, k, mask_h, seed):
-    g = torch.Generator().manual_seed(seed)
-    out = D * H
-    U = torch.randn(T, B, out * k, generator=g)
-    x = torch.randn(T, B, out, generator=g) if k == 3 and out > 1 else None
-    wc = torch.rand(2 * out, generator=g) * 2 - 1
-    bias = torch.cat([0.5 * torch.randn(out, generator=g), -torch.ones(out)])
-    mh = (torch.rand(B, out, generator=g) > 0.3).float() / 0.7 if mask_h else None
-    cot = torch.randn(T, B, out, generator=g)
-    return U, x, wc, bias, mh, cot
-
-
-def leaves(ts, dev, dtype):
-    return [None if t is None else t.to(device=dev, dtype=dtype).requires_grad_() for t in ts]
+def grade_scan(case):
+    """Y, Ym, dU, dweight_c, dbias and dx_skip - those the case has - of functional.sru_scan against the float64 reference."""
+    U, x, wc, bias, mh, cot, mn, cotm = (None if t is None else t.cuda() for t in scan_inputs(case))
+    ref, min_c = scan_reference(case)
+    if case.act in ("relu", "selu"):
+        assert min_c >= MIN_C
+    eU, ex, ewc, eb = leaves((U, x, wc, bias), "cuda", torch.float32)
+    got = F_.sru_scan(eU.clone(), ex, ewc, eb, 1.3, case.act, mask_h=mh, bidirectional=case.D == 2, mask_next=mn)
+    y, ym = got if mn is not None else (got, None)
+    scan_loss(case, y, ym, cot, cotm).backward()
+    got = {"Y": y, "Ym": ym, "dU": eU.grad, "dweight_c": ewc.grad, "dbias": eb.grad, "dx_skip": None if x is None else ex.grad}
+    assert sorted(ref) == sorted(n for n, t in got.items() if t is not None)
+    errs = {n: rel_err(got[n], ref[n]) for n in ref}
+    print("sru_scan", tuple(case), {n: "%.2e" % e for n, e in errs.items()})
+    assert max(errs.values()) < TOL, errs
 
 
 @pytest.mark.parametrize("T,B,D,H,k,act,mask_h,seed", SCAN)
 def test_scan_matches_reference(T, B, D, H, k, act, mask_h, seed):
-    U, x, wc, bias, mh, cot = scan_inputs(T, B, D, H, k, mask_h, seed)
-    rU, rx, rwc, rb = leaves((U, x, wc, bias), "cpu", torch.float64)
-    cs = []
-    ry = sru_scan_ref(rU, rx, rwc, rb, 1.3, act, D, None if mh is None else mh.double(), cs)
-    if act in ("relu", "selu"):
-        assert float(torch.stack(cs).detach().abs().min()) >= 1e-3
-    (ry * cot.double()).sum().backward()
-    eU, ex, ewc, eb = leaves((U, x, wc, bias), "cuda", torch.float32)
-    y = F_.sru_scan(eU.clone(), ex, ewc, eb, 1.3, act, mask_h=None if mh is None else mh.cuda(), bidirectional=D == 2)
-    (y * cot.cuda()).sum().backward()
-    errs = {"Y": rel_err(y, ry), "dU": rel_err(eU.grad, rU.grad), "dweight_c": rel_err(ewc.grad, rwc.grad),
-            "dbias": rel_err(eb.grad, rb.grad)}
-    if x is not None:
-        errs["dx_skip"] = rel_err(ex.grad, rx.grad)
-    print("sru_scan", (T, B, D, H, k, act, mask_h), {n: "%.2e" % e for n, e in errs.items()})
-    assert max(errs.values()) < TOL, errs
+    grade_scan(ScanCase(T, B, D, H, k, None, act, mask_h, None, seed))
+
+
+@pytest.mark.parametrize("case", RING, ids=[c.id for c in RING])
+def test_scan_ring_and_masked_copy_match_reference(case):
+    """The register ring's block loops at every hand-over, with the masked copy Ym = Y * mask_next graded by itself and each
+    set of output gradients (sru_cases.RING says which path a case is there for)."""
+    grade_scan(case)
+
+
+@pytest.mark.parametrize("case", LENS_CASES, ids=[c.id for c in LENS_CASES])
+def test_scan_lengths_give_every_sentence_alone(case):
+    U, x, wc, bias, mh, _, mn, _ = scan_inputs(case)
+    dev = [None if t is None else t.cuda() for t in (U, x, wc, bias)]
+    with torch.no_grad():
+        y, ym = F_.sru_scan(*dev, 1.3, case.act, mask_h=mh.cuda(), lens=LENS, bidirectional=True, mask_next=mn.cuda())
+    for b, n in enumerate(LENS):
+        ry = sru_scan_ref(U[:n, b:b + 1].double(), None if x is None else x[:n, b:b + 1].double(), wc.double(), bias.double(), 1.3,
+                          case.act, case.D, mh[b:b + 1].double())
+        e, em = rel_err(y[:n, b:b + 1], ry), rel_err(ym[:n, b:b + 1], ry * mn[b:b + 1].double())
+        print("sru_scan lens %s: sentence %d (%d steps) Y %.2e Ym %.2e" % (case.id, b, n, e, em))
+        assert e < TOL and em < TOL
+        assert not y[n:, b].any() and not ym[n:, b].any()
+
+
+def test_lengths_out_of_range_are_clamped_by_the_kernel():
+    """pk_sru_fwd itself: a length below 0 or above T - which functional.sentence_lengths never lets through - is "clamped
+    into 0 .. T" (include/pk_amd.h), so nothing is read outside U: 0 steps give zeros, 25 of 20 give all 20."""
+    case, (T, B, D, H, k) = CLAMP_CASE, CLAMP_CASE[:5]
+    U, _, wc, bias = scan_inputs(case)[:4]
+    dU, dwc, dbias = U.cuda(), wc.cuda(), bias.cuda()
+    lens = torch.tensor(CLAMP_LENS, dtype=torch.int32, device="cuda")
+    y = torch.full((T, B, D * H), float("nan"), device="cuda")
+    st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    rc = _lib.load().pk_sru_fwd(st, T, B, D, H, k, F_.SRU_ACT[case.act], dU.data_ptr(), None, 1.3, dwc.data_ptr(), dbias.data_ptr(),
+                                None, lens.data_ptr(), None, y.data_ptr(), None, None)
+    _lib.check(rc, "pk_sru_fwd")
+    for b, n in enumerate(min(max(n, 0), T) for n in CLAMP_LENS):
+        assert not y[n:, b].any()  # zeros, not the NaN the buffer held
+        if n:
+            ry = sru_scan_ref(U[:n, b:b + 1].double(), None, wc.double(), bias.double(), 1.3, case.act, D)
+            e = rel_err(y[:n, b:b + 1], ry)
+            print("pk_sru_fwd, lens[%d] = %d: %d steps, %.2e" % (b, CLAMP_LENS[b], n, e))
+            assert e < TOL
+    assert [min(max(n, 0), T) for n in CLAMP_LENS] == [0, 20, 0, 7]
+
+
+def test_mask_over_its_stride_loop():
+    """pk_sru_mask starts at most 4096 x 256 threads; with more elements than that each thread takes several.  One float32
+    multiply has one correct result: bit for bit, forward and backward."""
+    g = torch.Generator().manual_seed(3)
+    x, dy = (torch.randn(130, 33, 257, generator=g).cuda() for _ in range(2))
+    mask = (torch.rand(33, 257, generator=g) > 0.1).float().cuda() / 0.9
+    assert x.numel() > 4096 * 256
+    y = F_.sru_mask(x.requires_grad_(), mask)
+    y.backward(dy)
+    differ = int((y != x * mask).sum()), int((x.grad != dy * mask).sum())
+    print("sru_mask: %d elements, %d differ forward, %d backward" % ((x.numel(),) + differ))
+    assert torch.equal(y.detach(), x.detach() * mask) and torch.equal(x.grad, dy * mask)
 
 
 def options(H=10, layers=2, bidir=True, n_proj=0, skip=True, rescale=True, act="none", to_do="train"):
