@@ -505,8 +505,16 @@ int pk_quat_fold(void* stream, const float* dW, int G, int I, int O, float beta,
  * rounded to bf16 while staging, fp32 accumulation; dbias adds the unrounded dY).  bias may be NULL.  beta is 0 (overwrite,
  * the old contents are not read) or 1.  The four components are named by `comps` / `dcomps` (a HOST array of four device
  * pointers) or by `base` / `dbase` (back to back), the other being NULL, as for pk_quat_assemble.  N, I, O >= 1 of any
- * parity; I, O <= 2^20, I * O <= 2^30, N < 2^31, N * 4 * max(I, O) <= 2^40 (pk_quat_linear_work_floats gives 0 outside). */
+ * parity; I, O <= 2^20, I * O <= 2^30, N < 2^31, N * 4 * max(I, O) <= 2^40 (pk_quat_linear_work_floats gives 0 outside).
+ * Two kernel families serve each pass: variant 0 owns 32- or 64-row tiles and wins while the rows are few, variant 1 streams
+ * 128 x 64 block pairs through two LDS stages and wins once those give every CU about two workgroups (components narrower
+ * than one of its tiles stay with variant 0).  pk_quat_linear_variant says
+ * which one a call takes (pass 0 forward, 1 dX, 2 dcomp; 0 for arguments out of range), a plain function of its arguments and
+ * pk_num_cu(); pk_quat_linear_set_variant(0 / 1) forces one for every later call, -1 (the default) gives the rule back, as
+ * pk_gemm_bf16_set_tile does for the GEMM.  Both variants compute the same sums; the order of the additions differs. */
 int64_t pk_quat_linear_work_floats(int64_t N, int I, int O);
+int pk_quat_linear_variant(int pass, int prec, int64_t N, int I, int O);
+void pk_quat_linear_set_variant(int v);
 int pk_quat_linear_fwd(void* stream, int prec, int64_t N, int I, int O, const float* X, const float* const* comps,
                        const float* base, const float* bias, float* Y);
 int pk_quat_linear_bwd_x(void* stream, int prec, int64_t N, int I, int O, const float* dY, const float* const* comps,

@@ -138,6 +138,8 @@ SIGNATURES = {
     "pk_quat_assemble": (c_int, [P, P, P, c_int, c_int, c_int, P]),
     "pk_quat_fold": (c_int, [P, P, c_int, c_int, c_int, c_float, P, P]),
     "pk_quat_linear_work_floats": (c_int64, [c_int64, c_int, c_int]),
+    "pk_quat_linear_variant": (c_int, [c_int, c_int, c_int64, c_int, c_int]),
+    "pk_quat_linear_set_variant": (None, [c_int]),
     "pk_quat_linear_fwd": (c_int, [P, c_int, c_int64, c_int, c_int, P, P, P, P, P]),
     "pk_quat_linear_bwd_x": (c_int, [P, c_int, c_int64, c_int, c_int, P, P, P, P]),
     "pk_quat_linear_bwd_w": (c_int, [P, c_int, c_int64, c_int, c_int, P, P, c_float, P, P, P, P]),

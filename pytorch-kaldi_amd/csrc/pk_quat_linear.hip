@@ -42,8 +42,13 @@
 //
 // Precision.  PK_PREC_F32: v_mfma_f32_16x16x4_f32, exact fp32 products.  PK_PREC_BF16: operands rounded to bf16 (round to
 // nearest even, pk_f2bf - the rounding of the bf16 GEMM's staging) on their way into LDS, v_mfma_f32_16x16x32_bf16, fp32
-// accumulation.  No software pipelining across k steps: the loads of a step are hidden by the other workgroups of the CU
-// (26 .. 52 KB of LDS each).
+// accumulation.  No software pipelining across k steps in this family: the loads of a step are hidden by the other
+// workgroups of the CU (26 .. 52 KB of LDS each).
+//
+// Two families.  The one described so far (variant 0) serves calls with few rows.  The wide family further down (variant 1:
+// 128 x 64 block pairs, two LDS stages, the loads of step k + 1 in flight under the MFMAs of step k) serves sequence-sized
+// batches; ql_variant() holds the measured rule that picks one per (pass, precision, shape), pk_quat_linear_set_variant
+// forces either.  Both take the same QlArgs and sign masks and give the same sums in a different order.
 #include "pk_common.h"
 
 namespace {
@@ -288,6 +293,309 @@ __global__ __launch_bounds__(256) void ql_reduce_kernel(const float* __restrict_
     }
 }
 
+// ---- the wide family (variant 1): 128 x 64 block pairs streamed through two LDS stages -----------------------------------
+// A workgroup (four waves, 2 x 2) owns 128 rows of A by 64 rows of B and all four accumulator sets; a wave owns 4 x 2 MFMA
+// tiles of each set, 128 accumulator registers that stay put for the whole reduction.  Per k step (32 in bf16 mode, 16 in
+// fp32 mode: two stages of (4*128 + 4*64) rows are 120 KB resp. 108 KB of the CU's 160 KB) the global loads of step k + 1 go
+// into registers BEFORE the MFMAs of step k and are rounded and stored to the other stage AFTER them; one barrier per step
+// separates the reads of a stage from its next writes.  Pitches, load widths, zero fill, rounding and the sign flip are
+// those of the family above; the fp32 pitch of 18 floats spreads 16 rows x 2 k over 32 banks as 34 does.  The matrix
+// instruction takes the B fragment first, so that a lane's four accumulator elements run along the row index of B, which
+// is contiguous in the output: one 16-byte store per tile and row where pitch and base allow.
+constexpr int QW_TM = 128, QW_TW = 64, QW_RT = 4;
+// dcomp takes 32 rows of B: its slices are bounded by the workspace, and 128 x 32 block pairs are twice the workgroups
+constexpr int qw_tw(int mode) { return mode == QL_DW ? 32 : QW_TW; }
+// registers (16 bytes each) a thread holds of one operand's four [R][KC] tiles
+constexpr int qw_nv(int R, int KC) { return 4 * ((R * KC / 4 + QL_THREADS - 1) / QL_THREADS); }
+template <bool BF>
+struct QwGeo {
+    static constexpr int KC = BF ? 32 : 16;                                      // k per step
+    static constexpr int P = BF ? KC + 8 : KC + 2;                                // LDS row pitch (elements)
+    static constexpr int STAGE = 4 * (QW_TM + QW_TW) * P * (BF ? 2 : 4);          // bytes of one stage
+};
+static_assert(2 * QwGeo<true>::STAGE <= 160 * 1024 && 2 * QwGeo<false>::STAGE <= 160 * 1024, "both stages fit the LDS of a gfx950 CU");
+static_assert(QwGeo<true>::STAGE >= QL_THREADS * 16 * 4 && QwGeo<false>::STAGE >= QL_THREADS * 16 * 4, "the bias reduction reuses a stage");
+
+// The thread's share of the four [R][KC] tiles of one operand, global memory -> registers (element order of ql_stage).
+// R * KC / 256 16-byte loads, or four times as many 4-byte loads into the same registers.  No load is predicated: an index
+// past the valid part of the tile (rlim rows, klim of k, both >= 1) is clamped into it, and qw_store writes zero in its
+// place - held from here, the predicates of up to 96 loads in flight cost more scalar registers than there are.  The
+// address is a uniform 64-bit corner and a 32-bit offset (at most 127 * 2^22 + 2^20 elements).
+template <bool KCONT, int R, int KC>
+__device__ __forceinline__ void qw_load(f32x4 (&v)[qw_nv(R, KC)], const QlOp& op, long r0, long k0, int rlim, int klim) {
+    const int tid = threadIdx.x;
+    const long corner = KCONT ? r0 * op.ld + k0 : k0 * op.ld + r0;
+    const unsigned ld = (unsigned)op.ld;
+    if (op.vec) {  // (the contiguous extent is a multiple of 4: all four or none)
+        // (32 x 16 fp32: half a pass per block, the upper threads store nothing)
+        constexpr int C4 = (KCONT ? KC : R) / 4, NC = KCONT ? R : KC, PER = (NC * C4 + QL_THREADS - 1) / QL_THREADS;
+#pragma unroll
+        for (int j = 0; j < 4 * PER; ++j) {
+            const int blk = j / PER, idx = tid + (j % PER) * QL_THREADS;
+            const int c4 = idx % C4, run = idx / C4;
+            const int r = KCONT ? run : 4 * c4, k = KCONT ? 4 * c4 : run;
+            const int rc = min(r, rlim - (KCONT ? 1 : 4)), kc = min(k, klim - (KCONT ? 4 : 1));
+            v[j] = *reinterpret_cast<const f32x4*>(op.p[blk] + corner + (KCONT ? rc * ld + kc : kc * ld + rc));
+        }
+    } else {
+        constexpr int C = KCONT ? KC : R, NC = KCONT ? R : KC, PER = NC * C / QL_THREADS;
+#pragma unroll
+        for (int j = 0; j < 4 * PER; ++j) {
+            const int blk = j / PER, idx = tid + (j % PER) * QL_THREADS;
+            const int c = idx % C, run = idx / C;
+            const int r = KCONT ? run : c, k = KCONT ? c : run;
+            const int rc = min(r, rlim - 1), kc = min(k, klim - 1);
+            v[j / 4][j % 4] = (op.p[blk] + corner)[KCONT ? rc * ld + kc : kc * ld + rc];
+        }
+    }
+}
+
+// all ones where r < rlim and k < klim, else zero, in vector arithmetic: as compares, the masks of a stage's values would
+// be held in scalar register pairs
+__device__ __forceinline__ unsigned qw_inside(int r, int k, int rlim, int klim) { return (unsigned)(((r - rlim) & (k - klim)) >> 31); }
+
+// ... and registers -> one LDS stage as [block][row][k], zero outside rlim / klim, rounded to bf16 in bf16 mode.  SUM (dcomp's dY): the thread also
+// adds what it holds into bsum[blk][e]; its column(s) are the same in every step (256 % (R / 4) == 256 % R == 0).
+template <bool KCONT, bool BF, int R, int KC, bool SUM>
+__device__ __forceinline__ void qw_store(void* lds, const f32x4 (&v)[qw_nv(R, KC)], int vec, int rlim, int klim, float (&bsum)[4][4]) {
+    constexpr int P = QwGeo<BF>::P;
+    const int tid = threadIdx.x;
+    if (vec) {
+        constexpr int C4 = (KCONT ? KC : R) / 4, NC = KCONT ? R : KC, PER = (NC * C4 + QL_THREADS - 1) / QL_THREADS;
+#pragma unroll
+        for (int j = 0; j < 4 * PER; ++j) {
+            const int blk = j / PER, idx = tid + (j % PER) * QL_THREADS;
+            const int c4 = idx % C4, run = idx / C4;
+            const int r = KCONT ? run : 4 * c4, k = KCONT ? 4 * c4 : run;
+            if (NC * C4 % QL_THREADS != 0 && idx >= NC * C4) continue;
+            const f32x4 x = __builtin_bit_cast(f32x4, __builtin_bit_cast(u32x4, v[j]) & qw_inside(r, k, rlim, klim));
+            if (SUM) {
+#pragma unroll
+                for (int e = 0; e < 4; ++e) bsum[blk][e] += x[e];
+            }
+            const int at = (blk * R + r) * P + k;
+            if (KCONT) {
+                if (BF) {
+                    *reinterpret_cast<uint2*>(reinterpret_cast<unsigned short*>(lds) + at) = make_uint2(pk_pack_bf2(x[0], x[1]), pk_pack_bf2(x[2], x[3]));
+                } else {
+                    *reinterpret_cast<float2*>(reinterpret_cast<float*>(lds) + at) = make_float2(x[0], x[1]);
+                    *reinterpret_cast<float2*>(reinterpret_cast<float*>(lds) + at + 2) = make_float2(x[2], x[3]);
+                }
+            } else {
+#pragma unroll
+                for (int e = 0; e < 4; ++e) ql_put<BF>(lds, at + e * P, x[e]);
+            }
+        }
+    } else {
+        constexpr int C = KCONT ? KC : R, NC = KCONT ? R : KC, PER = NC * C / QL_THREADS;
+#pragma unroll
+        for (int j = 0; j < 4 * PER; ++j) {
+            const int blk = j / PER, idx = tid + (j % PER) * QL_THREADS;
+            const int c = idx % C, run = idx / C;
+            const int r = KCONT ? run : c, k = KCONT ? c : run;
+            const float x = __uint_as_float(__float_as_uint(v[j / 4][j % 4]) & qw_inside(r, k, rlim, klim));
+            if (SUM) bsum[blk][0] += x;
+            ql_put<BF>(lds, (blk * R + r) * P + k, x);
+        }
+    }
+}
+
+// the 16 signed block products of one k step for the wave's 4 x CT tiles (rows (4*wr + t)*16 .. of A, (CT*wc + u)*16 .. of B):
+// 4 * CT B fragments stay in registers, each of the 16 A fragments is read once, flipped once and feeds 4 * CT matrix
+// instructions
+template <int MODE, bool BF>
+__device__ __forceinline__ void qw_mma(const void* As, const void* Bs, f32x4 (&acc)[QW_RT][qw_tw(MODE) / 32][4], int wr, int wc, int lr, int lq) {
+    constexpr unsigned FLIP = ql_flips(MODE);
+    constexpr int BT = qw_tw(MODE), BCT = BT / 32;  // rows of B per workgroup, MFMA tiles of them per wave
+    constexpr int KC = QwGeo<BF>::KC, P = QwGeo<BF>::P;
+    if (!BF) {
+        const float* A = reinterpret_cast<const float*>(As);
+        const float* B = reinterpret_cast<const float*>(Bs);
+#pragma unroll
+        for (int kk = 0; kk < KC / 4; ++kk) {
+            const int k = 4 * kk + lq;
+            float bf[BCT][4];
+#pragma unroll
+            for (int u = 0; u < BCT; ++u)
+#pragma unroll
+                for (int y = 0; y < 4; ++y) bf[u][y] = B[(y * BT + (wc * BCT + u) * 16 + lr) * P + k];
+#pragma unroll
+            for (int t = 0; t < QW_RT; ++t) {
+#pragma unroll
+                for (int x = 0; x < 4; ++x) {
+                    const float a = A[(x * QW_TM + (wr * QW_RT + t) * 16 + lr) * P + k];
+                    const float na = __uint_as_float(__float_as_uint(a) ^ 0x80000000u);
+#pragma unroll
+                    for (int u = 0; u < BCT; ++u)
+#pragma unroll
+                        for (int y = 0; y < 4; ++y)
+                            acc[t][u][x ^ y] = __builtin_amdgcn_mfma_f32_16x16x4f32(bf[u][y], ((FLIP >> (4 * x + y)) & 1u) ? na : a, acc[t][u][x ^ y], 0, 0, 0);
+                }
+            }
+        }
+    } else {
+        const unsigned short* A = reinterpret_cast<const unsigned short*>(As);
+        const unsigned short* B = reinterpret_cast<const unsigned short*>(Bs);
+        u32x4 bf[BCT][4];
+#pragma unroll
+        for (int u = 0; u < BCT; ++u)
+#pragma unroll
+            for (int y = 0; y < 4; ++y) bf[u][y] = *reinterpret_cast<const u32x4*>(B + (y * BT + (wc * BCT + u) * 16 + lr) * P + 8 * lq);
+        // the A fragments of row tile t + 1 are read under the 32 MFMAs of row tile t; the scheduling fence keeps the
+        // compiler from hoisting all 16 reads (and their flipped copies) to the top, which would not fit the registers
+        u32x4 a[2][4];
+#pragma unroll
+        for (int x = 0; x < 4; ++x) a[0][x] = *reinterpret_cast<const u32x4*>(A + (x * QW_TM + wr * QW_RT * 16 + lr) * P + 8 * lq);
+#pragma unroll
+        for (int t = 0; t < QW_RT; ++t) {
+            if (t + 1 < QW_RT) {
+#pragma unroll
+                for (int x = 0; x < 4; ++x)
+                    a[(t + 1) & 1][x] = *reinterpret_cast<const u32x4*>(A + (x * QW_TM + (wr * QW_RT + t + 1) * 16 + lr) * P + 8 * lq);
+            }
+#pragma unroll
+            for (int x = 0; x < 4; ++x) {
+                const u32x4 na = a[t & 1][x] ^ 0x80008000u;
+#pragma unroll
+                for (int u = 0; u < BCT; ++u)
+#pragma unroll
+                    for (int y = 0; y < 4; ++y)
+                        acc[t][u][x ^ y] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, bf[u][y]),
+                                                                                   __builtin_bit_cast(bf16x8, ((FLIP >> (4 * x + y)) & 1u) ? na : a[t & 1][x]),
+                                                                                   acc[t][u][x ^ y], 0, 0, 0);
+            }
+            __builtin_amdgcn_sched_barrier(0);
+        }
+    }
+}
+
+// grid (B row tiles * A row tiles with the B tiles running fastest - the workgroups that share 128 rows of A are
+// neighbours in time -, 1, slices [dcomp; else 1]), block 256, 2 * STAGE bytes of dynamic LDS
+template <int MODE, bool BF>
+__global__ __launch_bounds__(QL_THREADS) void ql_wide_kernel(QlArgs g, int wtiles, int outvec) {
+    constexpr int KC = QwGeo<BF>::KC, STAGE = QwGeo<BF>::STAGE, ABYTES = 4 * QW_TM * QwGeo<BF>::P * (BF ? 2 : 4);
+    constexpr bool AK = MODE != QL_DW, BK = MODE == QL_DX;  // k is the contiguous index of A / of B
+    constexpr int BT = qw_tw(MODE), BCT = BT / 32;  // rows of B per workgroup, MFMA tiles of them per wave
+    extern __shared__ __attribute__((aligned(16))) unsigned char qw_lds[];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, lr = lane & 15, lq = lane >> 4, wr = wave & 1, wc = wave >> 1;
+    const long r0 = (long)(blockIdx.x / wtiles) * QW_TM, w0 = (long)(blockIdx.x % wtiles) * BT;
+    long kbeg = 0, kend = g.kw;
+    if (MODE == QL_DW) {
+        kbeg = (long)blockIdx.z * g.rows;
+        kend = kbeg + g.rows < g.kw ? kbeg + g.rows : g.kw;
+    }
+    const bool sum = MODE == QL_DW && g.pbias != nullptr && r0 == 0;
+    f32x4 acc[QW_RT][BCT][4];
+#pragma unroll
+    for (int t = 0; t < QW_RT; ++t)
+#pragma unroll
+        for (int u = 0; u < BCT; ++u)
+#pragma unroll
+            for (int c = 0; c < 4; ++c) acc[t][u][c] = f32x4{0.f, 0.f, 0.f, 0.f};
+    float bsum[4][4] = {};
+    f32x4 ra[qw_nv(QW_TM, KC)], rb[qw_nv(BT, KC)];
+    // the valid part of the tiles: rows of A, rows of B (fixed) and k of the step in flight, all >= 1
+    const int alim = (int)(g.a.rmax - r0 < QW_TM ? g.a.rmax - r0 : QW_TM), blim = (int)(g.b.rmax - w0 < BT ? g.b.rmax - w0 : BT);
+    int klim = (int)(kend - kbeg < KC ? kend - kbeg : KC);
+    qw_load<AK, QW_TM, KC>(ra, g.a, r0, kbeg, alim, klim);
+    qw_load<BK, BT, KC>(rb, g.b, w0, kbeg, blim, klim);
+    qw_store<AK, BF, QW_TM, KC, false>(qw_lds, ra, g.a.vec, alim, klim, bsum);
+    if (MODE == QL_DW && sum) qw_store<BK, BF, BT, KC, true>(qw_lds + ABYTES, rb, g.b.vec, blim, klim, bsum);
+    else qw_store<BK, BF, BT, KC, false>(qw_lds + ABYTES, rb, g.b.vec, blim, klim, bsum);
+    __syncthreads();
+    int cur = 0;
+    for (long k0 = kbeg; k0 < kend; k0 += KC) {  // (trip count: the slice's rows / KC, known at launch)
+        const bool more = k0 + KC < kend;
+        if (more) {
+            klim = (int)(kend - k0 - KC < KC ? kend - k0 - KC : KC);
+            qw_load<AK, QW_TM, KC>(ra, g.a, r0, k0 + KC, alim, klim);
+            qw_load<BK, BT, KC>(rb, g.b, w0, k0 + KC, blim, klim);
+        }
+        qw_mma<MODE, BF>(qw_lds + cur * STAGE, qw_lds + cur * STAGE + ABYTES, acc, wr, wc, lr, lq);
+        if (more) {
+            unsigned char* nxt = qw_lds + (cur ^ 1) * STAGE;
+            qw_store<AK, BF, QW_TM, KC, false>(nxt, ra, g.a.vec, alim, klim, bsum);
+            if (MODE == QL_DW && sum) qw_store<BK, BF, BT, KC, true>(nxt + ABYTES, rb, g.b.vec, blim, klim, bsum);
+            else qw_store<BK, BF, BT, KC, false>(nxt + ABYTES, rb, g.b.vec, blim, klim, bsum);
+        }
+        __syncthreads();  // stage cur is read, stage cur ^ 1 is written
+        cur ^= 1;
+    }
+    // accumulator element e of lane (lr, lq): B row 4*lq + e, A row lr of the 16 x 16 tile
+#pragma unroll
+    for (int t = 0; t < QW_RT; ++t) {
+        const long r = r0 + (wr * QW_RT + t) * 16 + lr;
+        if (r >= g.a.rmax) continue;
+#pragma unroll
+        for (int u = 0; u < BCT; ++u) {
+            const long w = w0 + (wc * BCT + u) * 16 + 4 * lq;
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                // dcomp: workspace[slice][c][i][o];  forward / dX: block c of row r
+                float* dst = MODE == QL_DW ? g.out + ((long)blockIdx.z * 4 + c) * g.ldo + r * g.outw + w : g.out + r * g.ldo + c * g.outw + w;
+                f32x4 o = acc[t][u][c];
+                if (MODE != QL_DW && g.bias != nullptr) {
+#pragma unroll
+                    for (int e = 0; e < 4; ++e)
+                        if (w + e < g.b.rmax) o[e] += g.bias[c * g.outw + w + e];
+                }
+                if (outvec) {  // (the width is a multiple of 4: all four or none)
+                    if (w < g.b.rmax) *reinterpret_cast<f32x4*>(dst) = o;
+                } else {
+#pragma unroll
+                    for (int e = 0; e < 4; ++e)
+                        if (w + e < g.b.rmax) dst[e] = o[e];
+                }
+            }
+        }
+    }
+    if (sum) {  // (block-uniform) column sums of the staged dY: the threads of a column, in ascending order
+        float* red = reinterpret_cast<float*>(qw_lds);
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) red[tid * 16 + q * 4 + e] = bsum[q][e];
+        __syncthreads();
+        const int q = tid / BT, o = tid % BT;
+        float s = 0.f;
+        if (g.b.vec) {
+            for (int m = 0; m < QL_THREADS / (BT / 4); ++m) s += red[(m * (BT / 4) + (o >> 2)) * 16 + q * 4 + (o & 3)];
+        } else {
+            for (int m = 0; m < QL_THREADS / BT; ++m) s += red[(m * BT + o) * 16 + q * 4];
+        }
+        if (tid < 4 * BT && w0 + o < g.b.rmax) g.pbias[((long)blockIdx.z * 4 + q) * g.outw + w0 + o] = s;
+    }
+}
+
+template <int MODE>
+int qw_launch(hipStream_t s, bool bf, dim3 grid, const QlArgs& g, int wtiles) {
+    const int outvec = g.outw % 4 == 0 && g.ldo % 4 == 0 && ((uintptr_t)g.out & 15) == 0;
+    const void* k = bf ? (const void*)ql_wide_kernel<MODE, true> : (const void*)ql_wide_kernel<MODE, false>;
+    const size_t lds = 2 * (bf ? QwGeo<true>::STAGE : QwGeo<false>::STAGE);
+    if (int rc = pk_grant_dynamic_lds(k, lds)) return rc;
+    if (bf) hipLaunchKernelGGL((ql_wide_kernel<MODE, true>), grid, dim3(QL_THREADS), lds, s, g, wtiles, outvec);
+    else hipLaunchKernelGGL((ql_wide_kernel<MODE, false>), grid, dim3(QL_THREADS), lds, s, g, wtiles, outvec);
+    PK_LAUNCH_CHECK();
+    return 0;
+}
+
+// Which family serves a call: -1 the rule, 0 / 1 forced (pk_quat_linear_set_variant).  The rule counts the 128 x 64 block
+// pairs of the pass's output (for dcomp: of the rows it reduces over) and takes the wide family from the smallest measured
+// row count on at which it beat the other by more than the 3 % spread between boxes, forward and forward + backward, fp32
+// and bf16 (profiles/quat_linear.json, 1024 -> 1024 on 256 CUs): 16 000 rows = 500 pairs, about two per CU.  At 2 048 rows
+// (64 pairs) it loses or ties.  The count scales with the CUs of the device.
+int g_ql_variant = -1;
+constexpr long QW_PAIRS = 500, QW_PAIRS_CUS = 256;
+int ql_variant(int pass, int prec, int64_t N, int I, int O) {
+    if (g_ql_variant >= 0) return g_ql_variant;
+    // only 1024 -> 1024 is measured: a call whose components do not fill one wide tile (the B rows of the pass, for dcomp
+    // also its 128 A rows) would run mostly padding there and stays where it was
+    if (pass == QL_DW ? (I < QW_TM || O < qw_tw(QL_DW)) : (pass == QL_DX ? I : O) < QW_TW) return 0;
+    const long pairs = (long)((N + QW_TM - 1) / QW_TM) * (((pass == QL_DX ? I : O) + QW_TW - 1) / QW_TW);
+    (void)prec;  // (one threshold serves both precisions today)
+    return pairs * QW_PAIRS_CUS >= QW_PAIRS * pk_num_cu() ? 1 : 0;
+}
+
 bool ql_aligned(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 // slices of the rows and rows per slice (a multiple of the k step): a function of the shape alone
@@ -343,6 +651,12 @@ int ql_rows(void* stream, int dx, int prec, int64_t N, int KW, int OW, const flo
     g.b.rmax = OW;
     g.kw = KW;
     g.out = out, g.ldo = 4L * OW, g.outw = OW, g.bias = bias;
+    if (ql_variant(dx ? QL_DX : QL_FWD, prec, N, dx ? OW : KW, dx ? KW : OW)) {
+        const long wtw = (OW + QW_TW - 1) / QW_TW;
+        const dim3 wgrid((unsigned)((N + QW_TM - 1) / QW_TM * wtw));
+        return dx ? qw_launch<QL_DX>(pk_stream(stream), prec == PK_PREC_BF16, wgrid, g, (int)wtw)
+                  : qw_launch<QL_FWD>(pk_stream(stream), prec == PK_PREC_BF16, wgrid, g, (int)wtw);
+    }
     const long wt = (OW + QL_TW - 1) / QL_TW;
     const int rt = (N + 63) / 64 * wt >= QL_FILL_RT2 ? 2 : 1;
     const dim3 grid((unsigned)((N + 32 * rt - 1) / (32 * rt)), (unsigned)wt), block(QL_THREADS);
@@ -364,11 +678,23 @@ int ql_rows(void* stream, int dx, int prec, int64_t N, int KW, int OW, const flo
 
 }  // namespace
 
+// the argument limits of pk_quat_linear_work_floats
+static bool ql_in_range(int64_t N, int I, int O) {
+    return !(N < 1 || I < 1 || O < 1 || I > (1 << 20) || O > (1 << 20) || (long)I * O > (1L << 30) || N > (1LL << 31) - 4096);
+}
+
 extern "C" int64_t pk_quat_linear_work_floats(int64_t N, int I, int O) {
-    if (N < 1 || I < 1 || O < 1 || I > (1 << 20) || O > (1 << 20) || (long)I * O > (1L << 30) || N > (1LL << 31) - 4096) return 0;
+    if (!ql_in_range(N, I, O)) return 0;
     long rows;
     const int64_t s = ql_slices(N, I, O, &rows);
     return s * (4LL * I * O + 4LL * O);
+}
+
+extern "C" void pk_quat_linear_set_variant(int v) { g_ql_variant = (v == 0 || v == 1) ? v : -1; }
+
+extern "C" int pk_quat_linear_variant(int pass, int prec, int64_t N, int I, int O) {
+    if (pass < QL_FWD || pass > QL_DW || (prec != PK_PREC_F32 && prec != PK_PREC_BF16) || !ql_in_range(N, I, O)) return 0;
+    return ql_variant(pass, prec, N, I, O);
 }
 
 extern "C" int pk_quat_linear_fwd(void* stream, int prec, int64_t N, int I, int O, const float* X, const float* const* comps,
@@ -412,9 +738,15 @@ extern "C" int pk_quat_linear_bwd_w(void* stream, int prec, int64_t N, int I, in
     g.pbias = dbias != nullptr ? workspace + (long)slices * 4 * IO : nullptr;
     const dim3 grid((unsigned)((I + 31) / 32), (unsigned)((O + QL_TW - 1) / QL_TW), (unsigned)slices), block(QL_THREADS);
     hipStream_t s = pk_stream(stream);
-    if (prec == PK_PREC_BF16) hipLaunchKernelGGL((ql_kernel<QL_DW, true, 1>), grid, block, 0, s, g);
-    else hipLaunchKernelGGL((ql_kernel<QL_DW, false, 1>), grid, block, 0, s, g);
-    PK_LAUNCH_CHECK();
+    if (ql_variant(QL_DW, prec, N, I, O)) {  // the same slices (every one of them holds rows), a quarter .. an eighth of the workgroups
+        const long wtw = (O + qw_tw(QL_DW) - 1) / qw_tw(QL_DW);
+        const dim3 wgrid((unsigned)((I + QW_TM - 1) / QW_TM * wtw), 1, (unsigned)slices);
+        if (int rc = qw_launch<QL_DW>(s, prec == PK_PREC_BF16, wgrid, g, (int)wtw)) return rc;
+    } else {
+        if (prec == PK_PREC_BF16) hipLaunchKernelGGL((ql_kernel<QL_DW, true, 1>), grid, block, 0, s, g);
+        else hipLaunchKernelGGL((ql_kernel<QL_DW, false, 1>), grid, block, 0, s, g);
+        PK_LAUNCH_CHECK();
+    }
     const long total = 4 * IO + (dbias != nullptr ? 4L * O : 0);
     hipLaunchKernelGGL(ql_reduce_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, workspace, slices, IO, (long)O,
                        beta != 0.0f ? 1 : 0, tab, dbase, dbias);
