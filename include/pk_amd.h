@@ -698,6 +698,25 @@ int pk_sincfast_bwd(void* stream, const float* x, const float* dy, const float* 
                     const float* window, const float* half, int B, int64_t n, int C, int K, int s, int p, int d, float sample_rate,
                     float min_low_hz, float min_band_hz, float* dlow, float* dband, float* dx, float* partial);
 
+/* ---- the `mse` cost of the [model] language (pk_mse.hip; utils.py:2289-2291 and :2415-2417,
+ * torch.mean((outs[inp1] - outs[inp2]) ** 2)), fp32 in every precision mode.
+ *   a, b: logical [rows][F] matrices, unit stride along a row, rows lda / ldb floats apart (lda, ldb >= F): a column slice
+ *   of the chunk tensor is read in place.  16-byte loads are used wherever the addresses allow them; nothing is required
+ *   beyond the 4-byte alignment of a float.
+ * pk_mse_fwd (utils.py:2289-2291, :2415-2417):  *loss = (1 / (rows*F)) * sum (a - b)^2, one partial sum per workgroup in
+ *   partial (>= pk_mse_partial_floats(rows, F) floats) added in a fixed order in double: no atomics, the same bits on every
+ *   run.  NaN and Inf propagate.
+ * pk_mse_bwd (what autograd records for the same lines):  da = (2 / (rows*F)) * *dloss * (a - b), db = -da, both dense
+ *   [rows][F]; either may be NULL and is then not written.  dloss is DEVICE memory: no host sync, one launch, graph safe.
+ * pk_mse_partial_floats (the scratch of pk_mse_fwd for utils.py:2289-2291, :2415-2417): 0 for a refused shape.
+ * Refused (2, with the numbers in pk_last_error, before any device call): rows or F below 1, a pitch below F, rows*F above
+ *   2^40, a NULL operand. */
+int64_t pk_mse_partial_floats(int64_t rows, int64_t F);
+int pk_mse_fwd(void* stream, const float* a, int64_t lda, const float* b, int64_t ldb, int64_t rows, int64_t F, float* partial,
+               float* loss);
+int pk_mse_bwd(void* stream, const float* a, int64_t lda, const float* b, int64_t ldb, int64_t rows, int64_t F, const float* dloss,
+               float* da, float* db);
+
 /* persistent-recurrence health: number of spin time-outs since the last reset
  * (host-mapped counter, readable without a device sync). */
 unsigned pk_persist_error_count(void);

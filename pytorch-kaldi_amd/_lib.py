@@ -165,6 +165,9 @@ SIGNATURES = {
     "pk_sincfast_partial_floats": (c_int64, [c_int, c_int64, c_int, c_int, c_int, c_int, c_int]),
     "pk_sincfast_bwd": (c_int, [P, P, P, P, P, P, P, P, c_int, c_int64, c_int, c_int, c_int, c_int, c_int, c_float, c_float,
                                 c_float, P, P, P, P]),
+    "pk_mse_partial_floats": (c_int64, [c_int64, c_int64]),
+    "pk_mse_fwd": (c_int, [P, P, c_int64, P, c_int64, c_int64, c_int64, P, P]),
+    "pk_mse_bwd": (c_int, [P, P, c_int64, P, c_int64, c_int64, c_int64, P, P, P]),
     "pk_persist_error_count": (ctypes.c_uint, []),
     "pk_persist_error_reset": (None, []),
     "pk_linear_bn_act_bf16_covers": (c_int, [c_int64, c_int64, c_int64]),

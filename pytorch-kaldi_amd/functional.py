@@ -2223,6 +2223,66 @@ def sinc_conv_fast(x, low_hz_, band_hz_, n_, window_, K, stride, padding, dilati
                                 min_band_hz)
 
 
+# ----------------------------------------------------------------------------
+# The `mse` line of the [model] language (csrc/pk_mse.hip; utils.py:2289-2291, :2415-2417)
+# ----------------------------------------------------------------------------
+def _rows_pitch(t):
+    """t as a logical [rows, F] matrix with unit stride along a row: (tensor, row pitch in floats).  The leading dimensions
+    collapse when they are contiguous among themselves - a slice inp[..., a:b] of a contiguous chunk always is -; any other
+    layout is copied once."""
+    if t.dim() == 0:
+        t = t.reshape(1)
+    F = t.shape[-1]
+    lead = [(n, s) for n, s in zip(t.shape[:-1], t.stride()[:-1]) if n != 1]
+    nested = all(lead[i][1] == lead[i + 1][0] * lead[i + 1][1] for i in range(len(lead) - 1))
+    ld = lead[-1][1] if lead else F
+    if (t.stride(-1) == 1 or F == 1) and nested and ld >= F:
+        return t, ld
+    return t.contiguous(), F
+
+
+_MSE_PARTIALS = {}
+
+
+class MseCostFn(torch.autograd.Function):
+    """torch.mean((a - b) ** 2) as one reduction launch (two when more than one workgroup takes part) and one backward
+    launch.  Saves the operands, not their difference; the loss and its gradients are the same bits on every run."""
+
+    @staticmethod
+    def forward(ctx, a, b):
+        _need_gpu(a, b)
+        if a.shape != b.shape or a.numel() == 0:
+            raise _lib.PkError("mse_cost: two non-empty tensors of one shape (got %s and %s)" % (tuple(a.shape), tuple(b.shape)))
+        lib = _lib.load()
+        (a2, lda), (b2, ldb) = _rows_pitch(a), _rows_pitch(b)
+        F = a2.shape[-1]
+        rows = a2.numel() // F
+        npart = _MSE_PARTIALS.get((rows, F))
+        if npart is None:  # (a step calls this with one or two shapes: the answer is kept)
+            npart = _MSE_PARTIALS[(rows, F)] = int(lib.pk_mse_partial_floats(rows, F))
+        part, loss = _new(npart, like=a), _new(1, like=a)
+        _lib.check(lib.pk_mse_fwd(_stream(), _p(a2), lda, _p(b2), ldb, rows, F, _p(part), _p(loss)), "pk_mse_fwd")
+        ctx.save_for_backward(a2, b2)
+        ctx.cfg = (lda, ldb, rows, F, a.shape)
+        return loss.view(())
+
+    @staticmethod
+    def backward(ctx, dloss):
+        a2, b2 = ctx.saved_tensors
+        lda, ldb, rows, F, shape = ctx.cfg
+        want_a, want_b = ctx.needs_input_grad
+        dloss = dloss.contiguous()
+        da = torch.empty(shape, device=a2.device, dtype=torch.float32) if want_a else None
+        db = torch.empty(shape, device=a2.device, dtype=torch.float32) if want_b else None
+        _lib.check(_lib.load().pk_mse_bwd(_stream(), _p(a2), lda, _p(b2), ldb, rows, F, _p(dloss), _p(da), _p(db)), "pk_mse_bwd")
+        return da, db
+
+
+def mse_cost(a, b):
+    """The mean of (a - b)^2 over all elements of two equal-shaped fp32 tensors, a 0-dim tensor.  Differentiable in both."""
+    return MseCostFn.apply(a, b)
+
+
 class LnLastActDropFn(torch.autograd.Function):
     """drop(act(LayerNorm(z))) behind a conv layer's max-pool as ONE launch each way (pk_ln_last_act_drop_*), the CNN /
     SincNet flavour of the reference's LayerNorm (features [C, L], statistics over the last dim:
